@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- validated edge-interpolants/sec of the MI355X motion-validation rake.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--edges E] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--edges E] [--dump-outputs DIR] [--full [--no-cpu]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs: it draws the edges, warms up, times K steps, writes the last
+step's results when --dump-outputs is given and prints the line.  --full adds the legs that take runs of
+their own (CPU baseline, parity against the CPU rake and the oracle, sphere_fk stream, full-mask mode,
+per-phase pass, reference-work roofline); without it those fields of the line are null.
 
 Workload (BASELINE.json configs[1], SURVEY.md §8(d) config 2, set B): Panda 7-DOF
 (PandaBase<0,0,0>), the 14-sphere cage of the reference's collision benchmark
@@ -51,7 +56,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--edges", type=int, default=1 << 20, help="edges per GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="validate: beside the headline also run the legs that take runs of their own -- the CPU "
+                         "baseline, parity against the CPU rake and the oracle, the sphere_fk stream, full-mask mode, "
+                         "the per-phase pass and the roofline's reference-work count.  Without it the run sets up, "
+                         "warms up, times the steps and prints the line (those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="validate / pair / capt: after the timed steps write what the last timed step returned as "
+                         "DIR/<name>.npy (float32; ranks above 0 write <name>.rank<r>.npy)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU baseline sample time")
     ap.add_argument("--oracle-edges", type=int, default=1 << 18,
                     help="edges checked against the scalar oracle (the CPU rake checks every edge)")
@@ -80,7 +93,27 @@ def parse():
     ap.add_argument("--scene", default="cage", choices=["cage", "table_pick"],
                     help="validate: the 14-sphere cage (the headline) or MotionBenchMaker table_pick_panda scene0001 "
                          "(tests/golden/panda_table_pick.npz)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.dump_outputs and a.workload not in ("validate", "pair", "capt"):
+        ap.error("--dump-outputs: not available for --workload " + a.workload)
+    return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, rank, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: the arrays a caller of the timed path receives (name -> device tensor), as float32
+    .npy files; every value is a small integer, so the conversion is exact.  At most 64 MB per rank: a
+    longer array is cut to a fixed seeded sample of its rows (ascending row order)."""
+    os.makedirs(path, exist_ok=True)
+    cap = limit // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        v = t.cpu().numpy()
+        if v.size > cap:
+            v = v[np.sort(np.random.default_rng(0).choice(len(v), cap, replace=False))]
+        fn = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(path, fn), v.astype(np.float32))
 
 
 def make_edges(torch, vamp, env, robot, n_edges, seed, dev, edge_set="B"):
@@ -148,22 +181,28 @@ def cpu_rake_baseline(vamp, env, robot, starts, goals, seconds):
             "cpu_model": cpu_model(), "ok_fraction": float(ok.mean())}, ok, nb, ne
 
 
-def scene_envs(vamp, scene):
+def scene_envs(vamp, scene, with_oracle=True):
     """(product Environment, oracle Env, description) of a validate scene: the 14-sphere cage, or
-    MotionBenchMaker table_pick_panda scene0001 as resolved obstacle rows (tests/golden/panda_table_pick.npz)."""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import oracle_py as op
+    MotionBenchMaker table_pick_panda scene0001 as resolved obstacle rows (tests/golden/panda_table_pick.npz).
+    with_oracle=False: the oracle is neither built nor loaded and its Env is None."""
+    oenv = None
+    if with_oracle:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import oracle_py as op
 
-    op.build()
-    env, oenv = vamp.Environment(), op.Env()
+        op.build()
+        oenv = op.Env()
+    env = vamp.Environment()
     if scene == "cage":
         for c in CAGE:
             env.add_sphere(vamp.Sphere(c, 0.2))
-            oenv.add_sphere(c, np.float32(0.2))
+            if oenv is not None:
+                oenv.add_sphere(c, np.float32(0.2))
         return env, oenv, "14-sphere cage"
     fx = np.load(os.path.join(ROOT, "tests", "golden", "panda_table_pick.npz"), allow_pickle=False)
     for k in ("spheres", "capsules", "zcapsules", "cuboids", "zcuboids"):
-        setattr(oenv, k, [list(r) for r in fx["env_" + k]])
+        if oenv is not None:
+            setattr(oenv, k, [list(r) for r in fx["env_" + k]])
     for row in fx["env_spheres"]:
         env.add_sphere(vamp.Sphere(row[0:3], float(row[3])))
     for row in np.concatenate([fx["env_cuboids"], fx["env_zcuboids"]]):
@@ -905,6 +944,8 @@ def run_pair(a, torch, dist, rank, world, dev, stream, ctx, vamp):
     ev = []
     wall = timed_steps(a, torch, dist, dev, world, step, ev)
     kern_ms = ev[0]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, {"ok": okd, "n_e": nb})
     # rake/early-exit units from the CPU rake on the same edges (bit-identical results), as configs[1]
     _, c_nb, c_ne = robot.cpu_validate_batch(starts.cpu().numpy(), goals.cpu().numpy(), env, threads=host_threads())
     units = float(8 * c_ne.astype(np.int64).sum())
@@ -1129,6 +1170,8 @@ def run_capt(a, torch, dist, rank, world, dev, stream, ctx, vamp):
     ev = []
     wall = timed_steps(a, torch, dist, dev, world, step, ev)
     kern_ms = ev[0]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, {"ok": ok})
     wall_max, units_all = reduce_over_ranks(dist, torch, wall, float(N), dev, world)
     # configs[2]'s "1M collision queries" as raw CAPT::collides_simd sphere queries (scenes.raw_queries:
     # x, y ~ U[-1, 1], z ~ U[0, 1.2], r ~ U[r_min, r_max]), outside the contract's timed region
@@ -1235,6 +1278,43 @@ def run_capt(a, torch, dist, rank, world, dev, stream, ctx, vamp):
     emit(line)
 
 
+def full_roofline(a, oenv, s_all, g_all, base, c_nb, c_ne, E, strong, kern_ms, head_ms, tail_ms, scan_ms, plain):
+    """--full: the validate line's roofline -- the plain fields plus the reference-work count (instrumented
+    oracle), the committed profile's executed-work and traffic figures and the per-phase pass."""
+    f_head, f_tail, f_edges = algorithmic_flops(oenv, s_all, g_all, base)
+    # O(n_e^2) back-step enumeration (vgpu_panda.hh rake_block: block k = k sequential subtractions):
+    # its float ops per edge on the tail's items (edges valid after block 0), against the tail's
+    # algorithmic work -- the cost a per-edge prefix kernel would remove (DESIGN.md §5b)
+    tail_items = c_ok_head_items(c_nb, c_ne)
+    backstep_ops = 56.0 * float((tail_items * (tail_items + 1) // 2).sum()) / max(1, len(c_nb))  # 7 rows x 8 lanes
+    achieved = f_head * E / (head_ms * 1e-3) / 1e12
+    prof_w = {("B", "000", "cage"): "validate", ("A", "000", "cage"): "validate_setA",
+              ("B", "000", "table_pick"): "validate_table_pick"}.get((a.edge_set, a.base, a.scene))
+    tf = traffic_fields(prof_w, E) if prof_w and not strong else {"traffic": None, "traffic_source": None}
+    return {
+        "kernel": plain["kernel"],
+        "bound": plain["bound"],
+        "peak": plain["peak"],
+        "unit": plain["unit"],
+        **utilisation(prof_w if not strong else None, E, kern_ms, (f_head + f_tail) * E),
+        **tf,
+        "traffic_measured_in_run": False,
+        "algorithmic_flops_per_launch": (f_head + f_tail) * E,
+        "algorithmic_flops_per_edge": f_head + f_tail,
+        "kernel_ms": kern_ms,
+        "algorithmic_bytes_per_launch": plain["algorithmic_bytes_per_launch"],
+        "hbm_frac": plain["hbm_frac"],
+        "algorithmic_flops_sample_edges": f_edges,
+        "backstep_subtract_flops_per_edge": backstep_ops,
+        "backstep_frac_of_tail": backstep_ops / max(f_tail, 1e-9),
+        "phase_ms": {"head": head_ms, "scan_and_count": scan_ms, "tail": tail_ms},
+        "phase_frac": phase_utilisation(prof_w, E, {"head": head_ms, "tail": tail_ms})
+        if prof_w and not strong else None,
+        "phase_reference_work_frac": {"head": achieved / FP32_PEAK_TFLOPS,
+                                      "tail": f_tail * E / (max(tail_ms, 1e-9) * 1e-3) / 1e12 / FP32_PEAK_TFLOPS},
+    }
+
+
 _OUT = None  # the process's real stdout (fd 1 is pointed at stderr while the bench runs)
 
 
@@ -1278,7 +1358,7 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    env, oenv, scene_desc = scene_envs(vamp, a.scene)
+    env, oenv, scene_desc = scene_envs(vamp, a.scene, with_oracle=a.full)
     base = (0, 0, 0) if a.base == "000" else (200, 200, 0)
     robot = vamp.PandaBase(*base)
 
@@ -1304,15 +1384,14 @@ def main():
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize(dev)
-    ok_frac = float(ok.float().mean().item())
     # Units: the reference's early exit counts the interpolants of the rake blocks
     # it evaluates -- up to and including an edge's first invalid block.  Those counts come from the
     # CPU rake on the same edges (bit-identical results, and it reports the first failing block);
     # the GPU's own results are compared with it edge by edge below.
     s_all, g_all = starts.cpu().numpy(), goals.cpu().numpy()
-    if not a.no_cpu and world == 1:
+    if a.full and not a.no_cpu and world == 1:
         cpu_leg, c_ok, c_nb, c_ne = cpu_rake_baseline(vamp, env, robot, s_all, g_all, a.cpu_seconds)
-    else:
+    else:  # one pass, for the units alone
         c_ok, c_nb, c_ne = robot.cpu_validate_batch(s_all, g_all, env, threads=host_threads())
     units_local = float(8 * c_ne.astype(np.int64).sum())       # rake_early_exit
     units_full_local = float(8 * c_nb.astype(np.int64).sum())  # every interpolant of every edge
@@ -1333,13 +1412,16 @@ def main():
         dist.barrier()
     wall = t1 - t0
     kern_ms = ev0.elapsed_time(ev1) / a.steps  # HIP events on the launch stream
+    ok_frac = float(ok.float().mean().item())
 
     wall_max, units_all = reduce_over_ranks(dist, torch, wall, units_local, dev, world)
     _, units_full_all = reduce_over_ranks(dist, torch, wall, units_full_local, dev, world)
+    if a.dump_outputs:  # what the last timed step returned to its caller: ok[] and n_e of every edge
+        dump_outputs(a.dump_outputs, rank, {"ok": ok, "n_e": nb})
 
     # secondary leg (untimed for the headline): the HBM-bound sphere_fk stream, 4M configs
     fk_leg = None
-    if a.fk_leg and rank == 0:
+    if a.full and a.fk_leg and rank == 0:
         nq = 1 << 22
         q = torch.rand((nq, 7), device=dev, dtype=torch.float32) * 6.0 - 3.0
         out = torch.empty((3, 59, nq), device=dev, dtype=torch.float32)
@@ -1363,7 +1445,7 @@ def main():
     # full-mask mode: every rake block of every edge evaluated and kept -- its own
     # timed pass over the same (device-resident) edges, HIP events on the launch stream
     full_mask = None
-    if not strong:
+    if a.full and not strong:
         cap = int(units_full_local // 8) + 64
         blk = torch.empty(cap, dtype=torch.uint8, device=dev)
         okm = torch.empty(E, dtype=torch.uint8, device=dev)
@@ -1389,32 +1471,37 @@ def main():
         del blk, okm
 
     # per-phase kernel time (HIP events inside the library, separate untimed pass)
-    ctx.set_profiling(True)
-    for _ in range(a.steps):
-        step()
-    torch.cuda.synchronize(dev)
-    phases = ctx.phase_times()
-    ctx.set_profiling(False)
-    calls = max(1, phases["calls"])
-    head_ms = phases["head_ms"] / calls
-    tail_ms = phases["tail_ms"] / calls
-    scan_ms = phases["scan_ms"] / calls
+    if a.full:
+        ctx.set_profiling(True)
+        for _ in range(a.steps):
+            step()
+        torch.cuda.synchronize(dev)
+        phases = ctx.phase_times()
+        ctx.set_profiling(False)
+        calls = max(1, phases["calls"])
+        head_ms = phases["head_ms"] / calls
+        tail_ms = phases["tail_ms"] / calls
+        scan_ms = phases["scan_ms"] / calls
 
     if rank == 0:
-        f_head, f_tail, f_edges = algorithmic_flops(oenv, s_all, g_all, base)
-        # O(n_e^2) back-step enumeration (vgpu_panda.hh rake_block: block k = k sequential subtractions):
-        # its float ops per edge on the tail's items (edges valid after block 0), against the tail's
-        # algorithmic work -- the cost a per-edge prefix kernel would remove
-        tail_items = c_ok_head_items(c_nb, c_ne)
-        backstep_ops = 56.0 * float((tail_items * (tail_items + 1) // 2).sum()) / max(1, len(c_nb))  # 7 rows x 8 lanes
-        achieved = f_head * E / (head_ms * 1e-3) / 1e12
-        prof_w = {("B", "000", "cage"): "validate", ("A", "000", "cage"): "validate_setA",
-                  ("B", "000", "table_pick"): "validate_table_pick"}.get((a.edge_set, a.base, a.scene))
-        tf = traffic_fields(prof_w, E) if prof_w and not strong else {"traffic": None, "traffic_source": None}
+        # what the timed steps alone give; --full adds the fields that take runs of their own
+        roofline = {
+            "kernel": "validate_motions step: staged bound/queue/children kernels of head and tail "
+                      "(vgpu_staged.hip), one call",
+            "bound": "valu",
+            "peak": FP32_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "kernel_ms": kern_ms,
+            "algorithmic_bytes_per_launch": EDGE_BYTES * E,
+            "hbm_frac": EDGE_BYTES * E / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        }
+        if a.full:
+            roofline = full_roofline(a, oenv, s_all, g_all, base, c_nb, c_ne, E, strong, kern_ms, head_ms, tail_ms,
+                                     scan_ms, roofline)
         cpu = None
         parity = None
         parity_failed = []
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             cpu = cpu_leg
             g_ok, g_nb = ok.cpu().numpy(), nb.cpu().numpy()
             parity = {"cpu_rake": parity_record(g_ok, g_nb, c_ok, c_nb, "mr-vamp_amd/csrc/cpu AVX2 rake, every edge"),
@@ -1430,6 +1517,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": ms_step,
             "higher_is_better": True,
             "scaling": a.scaling,
@@ -1455,29 +1543,7 @@ def main():
             "counting": "rake_early_exit: 8 x rake blocks the reference evaluates (through an edge's first invalid "
                         "block); value_full_mask_count counts 8 * n_e of every edge, evaluated or not",
             "value_full_mask_count": units_full_all * a.steps / wall_max,
-            "roofline": {
-                "kernel": "validate_motions step: staged bound/queue/children kernels of head and tail "
-                          "(vgpu_staged.hip), one call",
-                "bound": "valu",
-                "peak": FP32_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                **utilisation(prof_w if not strong else None, E, kern_ms, (f_head + f_tail) * E),
-                **tf,
-                "traffic_measured_in_run": False,
-                "algorithmic_flops_per_launch": (f_head + f_tail) * E,
-                "algorithmic_flops_per_edge": f_head + f_tail,
-                "kernel_ms": kern_ms,
-                "algorithmic_bytes_per_launch": EDGE_BYTES * E,
-                "hbm_frac": EDGE_BYTES * E / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "algorithmic_flops_sample_edges": f_edges,
-                "backstep_subtract_flops_per_edge": backstep_ops,
-                "backstep_frac_of_tail": backstep_ops / max(f_tail, 1e-9),
-                "phase_ms": {"head": head_ms, "scan_and_count": scan_ms, "tail": tail_ms},
-                "phase_frac": phase_utilisation(prof_w, E, {"head": head_ms, "tail": tail_ms})
-                if prof_w and not strong else None,
-                "phase_reference_work_frac": {"head": achieved / FP32_PEAK_TFLOPS,
-                                              "tail": f_tail * E / (max(tail_ms, 1e-9) * 1e-3) / 1e12 / FP32_PEAK_TFLOPS},
-            },
+            "roofline": roofline,
             "roofline_hbm_fk": fk_leg,
             "full_mask": full_mask,
             "cpu_baseline": cpu,

@@ -92,6 +92,44 @@ def _strong_worker(rank, world, port, q):
     q.put((rank, ok))
 
 
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """--dump-outputs: one float32 .npy per array, values unchanged; ranks above 0 get their own file names."""
+    import numpy as np
+
+    ok = torch.tensor([1, 0, 1, 1], dtype=torch.uint8)
+    n_e = torch.tensor([4, 2, 7, 1], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "d"), 0, {"ok": ok, "n_e": n_e})
+    bench.dump_outputs(str(tmp_path / "d"), 1, {"ok": ok})
+    got = np.load(tmp_path / "d" / "ok.npy")
+    assert got.dtype == np.float32 and got.tolist() == [1.0, 0.0, 1.0, 1.0]
+    assert np.load(tmp_path / "d" / "n_e.npy").tolist() == [4.0, 2.0, 7.0, 1.0]
+    assert np.array_equal(np.load(tmp_path / "d" / "ok.rank1.npy"), got)
+
+
+def test_dump_outputs_caps_a_large_array_with_a_fixed_sample(tmp_path):
+    """arrays above the size limit (64 MB by default): the same ascending sample of rows on every call, the
+    limit's bytes in all"""
+    import numpy as np
+
+    assert bench.DUMP_BYTES == 64 << 20
+    big = torch.arange(5000, dtype=torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0, {"ok": big % 2, "n_e": big}, limit=8000)
+    a, b = np.load(tmp_path / "a" / "n_e.npy"), np.load(tmp_path / "b" / "n_e.npy")
+    assert a.dtype == np.float32 and a.nbytes + np.load(tmp_path / "a" / "ok.npy").nbytes == 8000
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "ok.npy"), a % 2)
+
+
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "x"
+
+
 def test_strong_slices_gloo_ws3():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

@@ -29,13 +29,13 @@ spec_env() {  # SPEC -> "VAMP_AMD_LIB=... ENV=VAL ..."
   [ "$1" != "$v" ] && e=$(echo ${1#*:} | tr ',' ' ')
   echo "VAMP_AMD_LIB=$(lib $v) $e"
 }
-bench_args() {  # workload -> bench.py arguments
+bench_args() {  # workload -> bench.py arguments (--full: the summaries below read the roofline, phase and parity legs)
   case $1 in
-    validate_setA) echo "--edge-set A" ;;
-    table_pick) echo "--scene table_pick" ;;
-    prm_edges_full) echo "--workload prm_edges --vertices 2681709" ;;
-    rrtc_pair) echo "--workload rrtc --robot panda_pair" ;;
-    *) echo "--workload $1" ;;
+    validate_setA) echo "--full --edge-set A" ;;
+    table_pick) echo "--full --scene table_pick" ;;
+    prm_edges_full) echo "--full --workload prm_edges --vertices 2681709" ;;
+    rrtc_pair) echo "--full --workload rrtc --robot panda_pair" ;;
+    *) echo "--full --workload $1" ;;
   esac
 }
 summary() {  # bench line -> one summary line on stdout

@@ -1,6 +1,7 @@
-"""Collect the round's rocprofv3 outputs (gpurun_out/) into committed profiles/ files.
+"""Collect the round's rocprofv3 outputs (tools/profile_round.sh's OUTDIR, default bench_out) into committed
+profiles/ files.
 
-    python tools/profile_collect.py r01
+    python tools/profile_collect.py r01 [OUTDIR]
 """
 import collections
 import csv
@@ -12,7 +13,7 @@ import sys
 
 R = sys.argv[1] if len(sys.argv) > 1 else "r01"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, sys.argv[2] if len(sys.argv) > 2 else "bench_out")
 P = os.path.join(ROOT, "profiles")
 os.makedirs(P, exist_ok=True)
 
