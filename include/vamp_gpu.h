@@ -231,7 +231,11 @@ int vgpu_prm_neighbor_params(int dim, double space_measure, double gamma_scale, 
 /* The neighbour query build_roadmap runs for every vertex i (prm.hh:264-266, NN::nearest on
  * the vertices 0 .. i-1): at most k[i] of them within r[i] (distance <= r), nearest first,
  * distance = Space<dim>::distance (nn.hh:53-57).  Device pointers: V[n][dim] -> nbr[n][kmax],
- * dist[n][kmax], cnt[n].  dim in {6, 7, 8, 14}, kmax <= 64. */
+ * dist[n][kmax], cnt[n].  dim in {6, 7, 8, 14}, 1 <= kmax <= 64.  k and r are indexed by vertex
+ * and may hold any values: a k[i] above kmax is treated as kmax (a row has kmax slots, so
+ * cnt[i] <= kmax), k[i] = 0 or an r[i] below every distance gives cnt[i] = 0, r[i] = +inf admits
+ * every earlier vertex; vertices 0 and 1 (start, goal) query nothing whatever k says.  Slots
+ * at or beyond cnt[i] are left as the caller passed them. */
 int vgpu_roadmap_knn(vgpu_ctx *ctx, int dim, const float *V, size_t n, const uint32_t *k, const float *r,
                      uint32_t kmax, uint32_t *nbr, float *dist, uint32_t *cnt);
 /* Neighbour-query method of the context: 0 auto (a spatial index -- Morton-sorted tiles with
@@ -345,7 +349,8 @@ int vgpu_cpu_rrtc(const vgpu_robot *robot, vgpu_env *env, const float *start, co
  * mr-vamp_amd/csrc/cpu/vcpu_roadmap.cpp): an exact static k-d tree over V[n][dim] with per-subtree minimum
  * vertex indices, answering the causal query of each listed vertex q = queries[j] (the k[q] nearest of
  * vertices 0 .. q-1 within r[q], Space::distance in the AVX lane order) -- the same lists as
- * vgpu_roadmap_knn.  Rows j of nbr/dist [m][kmax] and cnt[m].  threads <= 0: every hardware thread. */
+ * vgpu_roadmap_knn, for any k and r: a k[q] above kmax is treated as kmax, vertices 0 and 1 query nothing.
+ * Rows j of nbr/dist [m][kmax] and cnt[m].  threads <= 0: every hardware thread. */
 int vgpu_cpu_roadmap_knn(int dim, const float *V, size_t n, const uint32_t *queries, size_t m, const uint32_t *k,
                          const float *r, uint32_t kmax, uint32_t *nbr, float *dist, uint32_t *cnt, int threads);
 

@@ -91,7 +91,7 @@ struct Key {
 void query(const KdTree& T, uint32_t q, uint32_t k, float r, std::vector<Key>& heap)
 {
     heap.clear();
-    if (k == 0 || q == 0) return;
+    if (k == 0 || q < 2) return;  // vertices 0, 1 (start, goal) query nothing (prm.hh:228-233), whatever k says
     const int dim = T.dim;
     const float* x = T.V + (size_t)q * dim;
     float diff[kMaxD];

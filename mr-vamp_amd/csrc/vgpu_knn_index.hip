@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kQBlock) void query_kernel(const float* __restrict_
     float me[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) me[d] = inq ? Vs[(size_t)p * D + d] : 0.0f;
-    const uint32_t k = live ? min(kq[i], (uint32_t)K) : 0u;
+    const uint32_t k = live ? min(kq[i], min(kmax, (uint32_t)K)) : 0u;  // rows hold kmax
     const float r = live ? rq[i] : -1.0f;
     float bd[K];
     uint32_t bi[K];
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(kQBlock) void group_kernel(const float* __restrict_
         const bool live = inq && qi[q] >= 2;  // vertices 0, 1 (start, goal) query nothing (prm.hh:228-233)
 #pragma unroll
         for (int d = 0; d < D; ++d) me[q][d] = unf(inq ? Vs[(size_t)p * D + d] : 0.0f);
-        kk[q] = uni(live ? min(kq[qi[q]], 64u) : 0u);
+        kk[q] = uni(live ? min(kq[qi[q]], min(kmax, 64u)) : 0u);  // rows hold kmax
         wd[q] = unf(live ? rq[qi[q]] : -1.0f);  // admission bound: r while fewer than k are held, else the k-th key
         wi[q] = 0xFFFFFFFFu;
         c[q] = 0;
@@ -854,7 +854,7 @@ __global__ __launch_bounds__(64 * WV) void coop_kernel(const float* __restrict__
         const bool live = inq && qi[q] >= 2;  // vertices 0, 1 (start, goal) query nothing (prm.hh:228-233)
 #pragma unroll
         for (int d = 0; d < D; ++d) me[q][d] = unf(inq ? Vs[(size_t)p * D + d] : 0.0f);
-        kk[q] = uni(live ? min(kq[qi[q]], 64u) : 0u);
+        kk[q] = uni(live ? min(kq[qi[q]], min(kmax, 64u)) : 0u);  // rows hold kmax
         wd[q] = unf(live ? rq[qi[q]] : -1.0f);
         wi[q] = 0xFFFFFFFFu;
         c[q] = 0;

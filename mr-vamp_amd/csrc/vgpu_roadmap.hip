@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kernel(const float* __restrict_
     float me[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) me[j] = (i < q_end) ? V[(size_t)i * D + j] : 0.0f;
-    const uint32_t k = live ? min(kq[i], (uint32_t)K) : 0u;  // k, r indexed by vertex
+    const uint32_t k = live ? min(kq[i], min(kmax, (uint32_t)K)) : 0u;  // k, r indexed by vertex; rows hold kmax
     const float r = live ? rq[i] : -1.0f;
     float bd[K];
     uint32_t bi[K];
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(uint32_t n, uint32_t q_f
     const uint32_t o = blockIdx.x * 256 + threadIdx.x;
     if (o >= q_count) return;
     const uint32_t i = q_first + o;
-    const uint32_t k = i >= 2 ? min(kq[i], (uint32_t)K) : 0u;
+    const uint32_t k = i >= 2 ? min(kq[i], min(kmax, (uint32_t)K)) : 0u;
     float bd[K];
     uint32_t bi[K];
 #pragma unroll

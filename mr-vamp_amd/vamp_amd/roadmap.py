@@ -125,15 +125,26 @@ def prm_neighbor_params(dim: int, space_measure: float, n: int, gamma_scale: flo
     return k, r
 
 
-def cpu_knn(V, queries, space_measure: float, gamma_scale: float = 2.0, kmax=None, threads: int = 0):
+def cpu_knn(V, queries, space_measure: float = 1.0, gamma_scale: float = 2.0, kmax=None, threads: int = 0,
+            k=None, r=None):
     """build_roadmap's causal neighbour queries of the listed vertices on the host CPU (exact k-d tree,
-    vgpu_cpu_roadmap_knn): (nbr [m, kmax], dist [m, kmax], cnt [m]) -- the lists vgpu_roadmap_knn gives."""
+    vgpu_cpu_roadmap_knn): (nbr [m, kmax], dist [m, kmax], cnt [m]) -- the lists vgpu_roadmap_knn gives.
+    k [n], r [n] (both or neither; indexed by vertex): the caller's parameters instead of the PRM* schedule
+    of space_measure and gamma_scale; a k[i] above kmax counts as kmax."""
     from . import _lib
     from ._lib import check, load
     V = np.ascontiguousarray(V, np.float32)
     n, dim = V.shape
     q = np.ascontiguousarray(queries, np.uint32).ravel()
-    k, r = prm_neighbor_params(dim, space_measure, n, gamma_scale)
+    if (k is None) != (r is None):
+        raise ValueError("cpu_knn: give both k and r, or neither")
+    if k is None:
+        k, r = prm_neighbor_params(dim, space_measure, n, gamma_scale)
+    else:
+        k = np.ascontiguousarray(k, np.uint32).ravel()
+        r = np.ascontiguousarray(r, np.float32).ravel()
+        if len(k) != n or len(r) != n:
+            raise ValueError("cpu_knn: k and r hold one entry per vertex")
     kmax = int(kmax or max(1, int(k.max()) if n else 1))
     nbr = np.zeros((max(len(q), 1), kmax), np.uint32)
     dist = np.zeros((max(len(q), 1), kmax), np.float32)

@@ -214,6 +214,10 @@ float vo_prm_neighbor_radius(int dim, double space_measure, double gamma_scale, 
 float vo_config_distance(const float *a, const float *b, int dim);
 void vo_roadmap_knn(int dim, const float *V, size_t n, double space_measure, double gamma_scale, uint32_t kmax,
                     uint32_t *nbr, float *dist, uint32_t *cnt, int threads);
+/* The same loop with caller-chosen parameters: k[n], r[n] indexed by vertex (k clamped to kmax), row j of
+ * nbr[m][kmax], dist, cnt answers vertex queries[j] (NULL: vertex j) against the vertices before it. */
+void vo_roadmap_knn_kr(int dim, const float *V, size_t n, const uint32_t *queries, size_t m, const uint32_t *k,
+                       const float *r, uint32_t kmax, uint32_t *nbr, float *dist, uint32_t *cnt, int threads);
 
 /* ---- Point-cloud filter (collision/filter.hh:101-121,175-268) ---- */
 /* remap_point (filter.hh:101-104): float quotient * 1000 converted to uint32 the way GCC's x86-64

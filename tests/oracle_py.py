@@ -686,6 +686,31 @@ def roadmap_knn(V, space_measure, gamma=2.0, kmax=None, threads=8):
     return nbr, dist, cnt
 
 
+def roadmap_knn_kr(V, k, r, kmax, queries=None, threads=8):
+    """The plain neighbour loop with caller-chosen parameters (vo_roadmap_knn_kr): k [n], r [n] indexed by
+    vertex (k clamped to kmax); row j answers vertex queries[j] (None: every vertex in order) against the
+    vertices before it.  Slots at or beyond cnt[j] stay 0."""
+    V = np.ascontiguousarray(V, np.float32)
+    n, dim = V.shape
+    k = np.ascontiguousarray(k, np.uint32).ravel()
+    r = np.ascontiguousarray(r, np.float32).ravel()
+    assert len(k) == n and len(r) == n and kmax >= 1
+    q = None if queries is None else np.ascontiguousarray(queries, np.uint32).ravel()
+    assert q is None or (len(q) == 0 or int(q.max()) < n)
+    m = n if q is None else len(q)
+    nbr = np.zeros((max(m, 1), kmax), np.uint32)
+    dist = np.zeros((max(m, 1), kmax), np.float32)
+    cnt = np.zeros(max(m, 1), np.uint32)
+    L = lib()
+    U32P_ = C.POINTER(C.c_uint32)
+    L.vo_roadmap_knn_kr.restype = None
+    L.vo_roadmap_knn_kr.argtypes = [C.c_int, F32P, C.c_size_t, U32P_, C.c_size_t, U32P_, F32P, C.c_uint32,
+                                    U32P_, F32P, U32P_, C.c_int]
+    L.vo_roadmap_knn_kr(dim, fp(V), n, None if q is None else q.ctypes.data_as(U32P_), m, k.ctypes.data_as(U32P_),
+                        fp(r), int(kmax), nbr.ctypes.data_as(U32P_), fp(dist), cnt.ctypes.data_as(U32P_), threads)
+    return nbr[:m], dist[:m], cnt[:m]
+
+
 def build_roadmap_edges(robot, env: Env, V, base100=(0, 0, 0), gamma=2.0, threads=8):
     """Roadmap::build_roadmap's graph (prm.hh:235-299) for the vertex sequence V (start, goal,
     valid samples in draw order): per vertex, its valid neighbours in query order (nearest
