@@ -24,6 +24,7 @@
 #include "vgpu_capt.hh"
 #include "vgpu_device.hh"
 #include "vgpu_host_env.hh"
+#include "vgpu_lean.hh"
 #include "vgpu_ops.hh"
 #include "gen/radii.inc"
 
@@ -44,7 +45,6 @@ hipError_t vgpu_launch_scatter_items(const uint32_t* cnt, const uint32_t* off, s
                                      hipStream_t st);
 hipError_t vgpu_launch_filter_robot(const float* pc, size_t n, float point_radius, const float* sph, int S,
                                    const EnvView* env, uint8_t* keep, hipStream_t st);
-hipError_t vgpu_launch_total64(const uint32_t* cnt, size_t n, unsigned long long* out, hipStream_t st);
 #define VGPU_STAGED_DECL(NAME)                                                                                       \
     int vgpu_##NAME##_staged_checks(void);                                                                           \
     uint64_t vgpu_##NAME##_staged_env_checks(void);                                                                  \
@@ -94,14 +94,14 @@ VGPU_STAGED_DECL(baxter_c4)
 VGPU_STAGED_DECL(baxter_c5)
 VGPU_STAGED_DECL(baxter_c6)
 hipError_t vgpu_launch_pair_tail_counts(const float* starts, const float* goals, size_t n_edges, const uint8_t* ok,
-                                        int32_t* n_blocks, uint32_t* cnt, hipStream_t st);
+                                        int32_t* n_blocks, uint32_t* cnt, const ItemTotalArgs* tot, hipStream_t st);
 const RobotOps* vgpu_ur5_ops(void);
 const RobotOps* vgpu_baxter_ops(void);
 hipError_t vgpu_launch_fetch_tail_counts(const float* starts, const float* goals, size_t n_edges, const uint8_t* ok,
-                                         int32_t* n_blocks, uint32_t* cnt, hipStream_t st);
+                                         int32_t* n_blocks, uint32_t* cnt, const ItemTotalArgs* tot, hipStream_t st);
 hipError_t vgpu_launch_mask_finish(size_t n_edges, const uint32_t* off, uint8_t* ok, uint8_t* block_ok, hipStream_t st);
 hipError_t vgpu_launch_tail_counts(const float* starts, const float* goals, size_t n_edges, const uint8_t* ok,
-                                   int32_t* n_blocks, uint32_t* cnt, hipStream_t st);
+                                   int32_t* n_blocks, uint32_t* cnt, const ItemTotalArgs* tot, hipStream_t st);
 hipError_t vgpu_launch_capt_grid(float* base, const vgpu::CaptGridArgs* g, hipStream_t st);
 hipError_t vgpu_launch_capt_query(const float* centers, const float* radii, size_t n, const EnvView* env, int index,
                                   int simd, uint8_t* out, hipStream_t st);
@@ -250,7 +250,10 @@ struct vgpu_ctx {
     size_t ws_bytes = 0;
     uint32_t* items = nullptr;
     size_t items_cap = 0;
-    uint32_t* total_host = nullptr;  // pinned, 4 words: [0] the 32-bit scan total, [2..3] its 64-bit sum
+    uint32_t* total_host = nullptr;  // pinned, 4 words: [0] the kNN edge count, [2..3] the back-step items' 64-bit total
+    // device words that are zero between calls (their kernels reset them, vgpu_kernels.hip): [0] the staged scan's
+    // ticket, [1] the item total's ticket, [2..3] its 64-bit accumulator
+    uint32_t* tick = nullptr;
     // compaction workspace (selected indices' count word + hipcub temp)
     void* aux = nullptr;
     size_t aux_bytes = 0;
@@ -268,9 +271,9 @@ struct vgpu_ctx {
     size_t st_mask_cap = 0;
     uint32_t* st_q = nullptr;  // staged sampling without a caller buffer: the drawn configurations
     size_t st_q_cap = 0;
-    uint32_t* st_cnt = nullptr;   // per-(check, block) counts, then their exclusive scan, + scan temp
+    uint32_t* st_cnt = nullptr;   // per-(check, block) counts, their per-check exclusive scan, the plan, totals
     size_t st_cnt_cap = 0;
-    uint32_t* st_host = nullptr;  // pinned: the first round's segment boundaries of a staged pass
+    uint32_t* st_host = nullptr;  // pinned: the first round's per-check totals of a staged pass, stored by its scan
     uint32_t* st_items = nullptr;
     size_t st_items_cap = 0;
     // roadmap kNN chunk lists (vgpu_roadmap.hip)
@@ -384,8 +387,11 @@ try {
     }
     if (hipMalloc(&c->lut_dev, c->lut.size() * 4) != hipSuccess ||
         hipMemcpy(c->lut_dev, c->lut.data(), c->lut.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc((void**)&c->dbg, 16) != hipSuccess || hipMemset(c->dbg, 0, 16) != hipSuccess) {
+        hipMalloc((void**)&c->dbg, 16) != hipSuccess || hipMemset(c->dbg, 0, 16) != hipSuccess ||
+        hipMalloc((void**)&c->tick, 16) != hipSuccess || hipMemset(c->tick, 0, 16) != hipSuccess) {
         if (c->lut_dev) (void)hipFree(c->lut_dev);
+        if (c->dbg) (void)hipFree(c->dbg);
+        if (c->tick) (void)hipFree(c->tick);
         (void)hipStreamDestroy(c->own);
         delete c;
         return VGPU_ERR_HIP;
@@ -442,6 +448,7 @@ extern "C" void vgpu_ctx_destroy(vgpu_ctx* c)
     if (c->knn_idx) (void)hipFree(c->knn_idx);
     if (c->small) (void)hipFree(c->small);
     if (c->dbg) (void)hipFree(c->dbg);
+    if (c->tick) (void)hipFree(c->tick);
     if (c->total_host) (void)hipHostFree(c->total_host);
     for (auto& ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -1399,8 +1406,12 @@ static StagedChain generic_chain(int32_t kind)
 }
 
 // One staged pass (vgpu_staged.hh) over n groups:
-//   bound -> count(all checks) -> scan -> [read back the per-check counts: the pass's ONE sync]
-//   -> per round: (count -> scan, later rounds) -> plan -> queue -> children per class.
+//   bound -> count(all checks) -> scan -> [the per-check totals, stored by the scan into pinned memory: the
+//   pass's ONE sync]  -> per round: (count -> scan, later rounds) -> queue -> children per class.
+// The scan (vgpu_kernels.hip staged_scan_kernel, one block per check) also lays out the round's plan whenever
+// the round's check set is known when it launches: every round after the first, and the first of a pass whose
+// rounds do not depend on the batch (one-round kinds, VAMP_AMD_ROUNDS).  Only the first round of a pass that
+// picks its rounds from the totals runs plan_kernel, over the boundaries the scan left.
 // The first round's per-check counts bound every later round's (groups only ever become invalid),
 // so they size all item buffers and children grids; the exact per-round layout is computed on the
 // device (plan_kernel) and read there by queue and children.
@@ -1421,19 +1432,18 @@ static int staged_pass(vgpu_ctx* c, const StagedOps& ops_in, int kind, const voi
     const uint32_t W = (kind >= 2) ? 8u : 64u;  // items per wave: 64 lanes / group size
     const size_t nb = ops.blocks(kind, (uint32_t)n);
     const size_t cells = (size_t)checks * nb;
-    const size_t scan_bytes = vgpu_validate_scan_bytes(cells);
-    const size_t cells_al = (cells + 1 + 63) & ~(size_t)63;
+    const size_t cells_al = (cells + 63) & ~(size_t)63;
     const size_t plan_words = ((ops.plan_bytes() + 3) / 4 + 63) & ~(size_t)63;  // keeps tmp 256-B aligned
     int rc;
     if (!masks_ready && (rc = grow(c, &c->st_mask, &c->st_mask_cap, n * (size_t)ops.mask_bytes() / 4))) return rc;
     uint32_t* const mask = c->st_mask + mask_off;
-    if ((rc = grow(c, &c->st_cnt, &c->st_cnt_cap, 2 * cells_al + scan_bytes / 4 + 64 + plan_words))) return rc;
+    if ((rc = grow(c, &c->st_cnt, &c->st_cnt_cap, 2 * cells_al + plan_words + 192))) return rc;
     if (!c->st_host) HIPCHK(c, hipHostMalloc((void**)&c->st_host, 128 * sizeof(uint32_t), hipHostMallocDefault));
     uint32_t* counts = c->st_cnt;
     uint32_t* offs = c->st_cnt + cells_al;
     void* plan = c->st_cnt + 2 * cells_al;
-    void* tmp = c->st_cnt + 2 * cells_al + plan_words;
-    HIPCHK(c, hipMemsetAsync(counts + cells, 0, sizeof(uint32_t), c->cur));
+    uint32_t* const tot = c->st_cnt + 2 * cells_al + plan_words;  // [64] the scan's per-check totals
+    uint32_t* const bnd = tot + 64;                               // [65] their running sum
     // the lead pass: one check for every group first (it initialises the flags), the rest chained
     const int lead = ops.lead_check();
     const unsigned lead_kinds = c->lead >= 0 ? (unsigned)c->lead : ops.lead_kinds;
@@ -1460,16 +1470,23 @@ static int staged_pass(vgpu_ctx* c, const StagedOps& ops_in, int kind, const voi
     if (use_lead) all &= ~(1ull << lead);  // decided by the lead pass
     const uint64_t env_bits = ops.env_checks();
     const int ext = (v->n_hf > 0 || v->n_pc > 0) ? 1 : 0;  // the children kernels' EXT instantiation (class table)
-    // every check's fired groups (groups still valid): segment boundaries offs[k * nb], k = 0..checks
+    StagedClassTable cls{};
+    for (int k = 0; k < checks; ++k) cls.of[k] = (uint8_t)ops.child_class(k, ext);
+    std::vector<uint64_t> rounds(c->rounds.begin(), c->rounds.end());
+    const unsigned one_round = c->one_round >= 0 ? (unsigned)c->one_round : ops.one_round_kinds;
+    if (rounds.empty() && ((one_round >> kind) & 1u)) rounds = {all};
+    // the first round's set when it does not depend on this batch: its plan comes out of the first scan
+    const bool planned = !rounds.empty();
+    const uint64_t planned_set = planned ? (rounds[0] & all) : 0;
+    // every check's fired groups (groups still valid): per-check totals tot[k], offs relative within a check
     HIPCHK(c, ops.count(kind, s0, s1, s2, s3, mask, (uint32_t)n, all, valid, counts, c->cur));
-    HIPCHK(c, vgpu_launch_scan(counts, offs, cells, tmp, scan_bytes, c->cur));
-    HIPCHK(c, hipMemcpy2DAsync(c->st_host, sizeof(uint32_t), offs, nb * sizeof(uint32_t), sizeof(uint32_t), checks + 1,
-                               hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, vgpu_launch_staged_scan(counts, offs, (uint32_t)nb, checks, tot, bnd, c->tick, c->st_host,
+                                      planned ? plan : nullptr, &cls, planned_set, W, (uint32_t)n, c->cur));
     if (c->stats && kind == 2 && s3)  // the compacted head list's live count (statistics only)
         HIPCHK(c, hipMemcpyAsync(c->st_host + 127, s3, sizeof(uint32_t), hipMemcpyDeviceToHost, c->cur));
     HIPCHK(c, hipStreamSynchronize(c->cur));
     uint32_t fired[64];
-    for (int k = 0; k < checks; ++k) fired[k] = c->st_host[k + 1] - c->st_host[k];
+    for (int k = 0; k < checks; ++k) fired[k] = c->st_host[k];
     if (c->stats) {  // VAMP_AMD_STAGED_STATS=1: the pass's bounding statistics (development)
         std::fprintf(stderr, "staged kind=%d chain=%d groups=%zu", kind, chain, n);
         if (kind == 2 && s3) std::fprintf(stderr, " live=%u", c->st_host[127]);
@@ -1477,9 +1494,6 @@ static int staged_pass(vgpu_ctx* c, const StagedOps& ops_in, int kind, const voi
         for (int k = 0; k < checks; ++k) std::fprintf(stderr, " %u", fired[k]);
         std::fprintf(stderr, "\n");
     }
-    std::vector<uint64_t> rounds(c->rounds.begin(), c->rounds.end());
-    const unsigned one_round = c->one_round >= 0 ? (unsigned)c->one_round : ops.one_round_kinds;
-    if (rounds.empty() && ((one_round >> kind) & 1u)) rounds = {all};
     if (rounds.empty()) {
         // Rounds from this batch's bounding statistics: (1) the environment check that fires for
         // the most groups, alone (the Panda's link-5 sphere: it fires for ~every group of an
@@ -1509,10 +1523,13 @@ static int staged_pass(vgpu_ctx* c, const StagedOps& ops_in, int kind, const voi
         if (!(ub[0] | ub[1] | ub[2] | ub[3])) continue;
         if (!first_round) {
             HIPCHK(c, ops.count(kind, s0, s1, s2, s3, mask, (uint32_t)n, set, valid, counts, c->cur));
-            HIPCHK(c, vgpu_launch_scan(counts, offs, cells, tmp, scan_bytes, c->cur));
+            HIPCHK(c, vgpu_launch_staged_scan(counts, offs, (uint32_t)nb, checks, tot, bnd, c->tick, nullptr, plan,
+                                              &cls, set, W, (uint32_t)n, c->cur));
+        } else if (!planned || set != planned_set) {
+            // the first scan ran before this set was chosen: plan_kernel over its boundaries (stride 1)
+            HIPCHK(c, ops.plan(bnd, 1u, W, set, (uint32_t)n, plan, ext, c->cur));
         }
         first_round = false;
-        HIPCHK(c, ops.plan(offs, (uint32_t)nb, W, set, (uint32_t)n, plan, ext, c->cur));
         HIPCHK(c, ops.queue(kind, s0, s1, s2, s3, mask, (uint32_t)n, set, plan, valid, offs, c->st_items, v->base,
                             c->cur));
         HIPCHK(c, ops.children(kind, s0, s1, s2, s3, first, plan, ub, c->st_items, v, bases, valid, c->cur));
@@ -1606,17 +1623,20 @@ try {
 // The back-step item count of a validate call (cnt[0 .. n_edges) scanned into off): read back once,
 // with its 64-bit sum -- the scan and the item indices are 32-bit, so a batch whose rake blocks do not
 // fit (very long edges) is rejected before any offset is used.
-static int item_total(vgpu_ctx* c, const uint32_t* cnt, const uint32_t* off, size_t n_edges, void* tmp,
-                      size_t tmp_bytes, size_t* n_items)
+// The kernel that wrote the counts sums them (the staged pipelines' tail_counts kernels; after a monolithic head,
+// item_total_kernel) and its last block stores the total into the pinned word itself: no fill, no copy command.  A
+// 64-bit total below 2^32 - n_edges is also what the 32-bit scan holds in off[n_edges], so that word is not read.
+static ItemTotalArgs total_args(vgpu_ctx* c)
 {
-    auto* t64 = (unsigned long long*)(((uintptr_t)tmp + tmp_bytes + 7) & ~(uintptr_t)7);
-    HIPCHK(c, vgpu_launch_total64(cnt, n_edges, t64, c->cur));
-    HIPCHK(c, hipMemcpyAsync(c->total_host, off + n_edges, sizeof(uint32_t), hipMemcpyDeviceToHost, c->cur));
-    HIPCHK(c, hipMemcpyAsync(c->total_host + 2, t64, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->cur));
+    return ItemTotalArgs{(unsigned long long*)(c->tick + 2), c->tick + 1, (unsigned long long*)(c->total_host + 2)};
+}
+
+static int item_total(vgpu_ctx* c, size_t n_edges, size_t* n_items)
+{
     HIPCHK(c, hipStreamSynchronize(c->cur));
     unsigned long long total = 0;
     std::memcpy(&total, c->total_host + 2, sizeof(total));
-    if (total != (unsigned long long)c->total_host[0] || total + n_edges >= (1ull << 32))
+    if (total + n_edges >= (1ull << 32))
         return fail(c, VGPU_ERR_INVALID_ARG, "edges too long: more than 2^32 rake blocks in one call (split the batch)");
     *n_items = (size_t)total;
     return VGPU_OK;
@@ -1626,7 +1646,7 @@ static int ensure_ws(vgpu_ctx* c, size_t n_edges, uint32_t** cnt, uint32_t** off
 {
     const size_t idx_bytes = ((n_edges + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
     *tmp_bytes = vgpu_validate_scan_bytes(n_edges);
-    const size_t need = 2 * idx_bytes + *tmp_bytes + 256;
+    const size_t need = 2 * idx_bytes + *tmp_bytes;
     if (need > c->ws_bytes) {
         if (c->ws) {
             HIPCHK(c, hipStreamSynchronize(c->cur));
@@ -1666,6 +1686,8 @@ try {
     void* tmp;
     size_t tmp_bytes;
     if ((rc = ensure_ws(c, n_edges, &cnt, &off, &tmp, &tmp_bytes))) return rc;
+    const ItemTotalArgs tot = total_args(c);
+    bool summed = false;  // the counts' total: by the staged tail_counts kernels themselves
     const bool pair_staged_path = r->kind == VGPU_ROBOT_PANDA_PAIR && c->staged;  // chained staged passes
     const bool pair = r->kind == VGPU_ROBOT_PANDA_PAIR && !c->staged;             // monolithic head/tail kernels
     const bool fetch = r->kind == VGPU_ROBOT_FETCH && !c->staged;
@@ -1688,7 +1710,8 @@ try {
         HIPCHK(c, g->validate_head(starts, goals, n_edges, &v, ok, n_blocks, cnt, c->cur));
     } else if (pair_staged_path) {
         if ((rc = pair_staged(c, 2, starts, goals, nullptr, nullptr, n_edges, &v, pb, ok))) return rc;
-        HIPCHK(c, vgpu_launch_pair_tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, c->cur));
+        HIPCHK(c, vgpu_launch_pair_tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, &tot, c->cur));
+        summed = true;
     } else if (pair) {
         HIPCHK(c, vgpu_launch_pair_validate_head(starts, goals, n_edges, &v, pb, ok, n_blocks, cnt, c->cur));
     } else if (fetch) {
@@ -1696,20 +1719,23 @@ try {
     } else if (c->staged) {
         if ((rc = chain_pass(c, chain, 2, starts, goals, nullptr, nullptr, 0, n_edges, &v, b, ok))) return rc;
         if (g)
-            HIPCHK(c, g->tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, c->cur));
+            HIPCHK(c, g->tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, &tot, c->cur));
         else if (r->kind == VGPU_ROBOT_FETCH)
-            HIPCHK(c, vgpu_launch_fetch_tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, c->cur));
+            HIPCHK(c, vgpu_launch_fetch_tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, &tot, c->cur));
         else
-            HIPCHK(c, vgpu_launch_tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, c->cur));
+            HIPCHK(c, vgpu_launch_tail_counts(starts, goals, n_edges, ok, n_blocks, cnt, &tot, c->cur));
+        summed = true;
     } else {
         HIPCHK(c, vgpu_launch_panda_validate_head(starts, goals, n_edges, &v, b[0], b[1], b[2], ok, n_blocks, cnt,
                                                   c->cur));
     }
     if (c->prof) HIPCHK(c, hipEventRecord(c->ev[1], c->cur));
+    // after a monolithic head: the total, and the scan's last input cnt[n_edges], before the scan reads it
+    if (!summed) HIPCHK(c, vgpu_launch_item_total(cnt, n_edges, &tot, c->cur));
     HIPCHK(c, vgpu_launch_scan(cnt, off, n_edges, tmp, tmp_bytes, c->cur));
     // number of back-step work items: one read-back (the item buffer is sized from it)
     size_t n_items = 0;
-    if ((rc = item_total(c, cnt, off, n_edges, tmp, tmp_bytes, &n_items))) return rc;
+    if ((rc = item_total(c, n_edges, &n_items))) return rc;
     if (n_items > c->items_cap) {
         if (c->items) HIPCHK(c, hipFree(c->items));
         c->items = nullptr;
@@ -1781,11 +1807,12 @@ try {
     void* tmp;
     size_t tmp_bytes;
     if ((rc = ensure_ws(c, n_edges, &cnt, &off, &tmp, &tmp_bytes))) return rc;
+    const ItemTotalArgs tot = total_args(c);
     if ((rc = staged_pass(c, kPandaStaged, 2, starts, goals, nullptr, nullptr, 0, n_edges, &v, b, ok))) return rc;
-    HIPCHK(c, vgpu_launch_tail_counts(starts, goals, n_edges, nullptr, n_blocks, cnt, c->cur));  // every back-step
+    HIPCHK(c, vgpu_launch_tail_counts(starts, goals, n_edges, nullptr, n_blocks, cnt, &tot, c->cur));  // every back-step
     HIPCHK(c, vgpu_launch_scan(cnt, off, n_edges, tmp, tmp_bytes, c->cur));
     size_t n_items = 0;
-    if ((rc = item_total(c, cnt, off, n_edges, tmp, tmp_bytes, &n_items))) return rc;
+    if ((rc = item_total(c, n_edges, &n_items))) return rc;
     *n_total = n_items + n_edges;
     if (!block_ok || block_cap < *n_total)
         return fail(c, VGPU_ERR_INVALID_ARG, "block_ok capacity < total blocks (*n_total)");

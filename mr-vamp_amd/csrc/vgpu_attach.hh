@@ -61,8 +61,7 @@ struct AttHost {
     static hipError_t head(const float* starts, const float* goals, size_t n_edges, const EnvView* env, uint8_t* ok,
                            int32_t* n_blocks, uint32_t* cnt, hipStream_t st)
     {
-        hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-        if (err != hipSuccess || n_edges == 0) return err;
+        if (n_edges == 0) return hipSuccess;  // cnt[n_edges]: written by item_total_kernel, which runs before the scan
         const unsigned grid = (unsigned)((n_edges * 8 + kAttBlock - 1) / kAttBlock);
         if (env->n_hf > 0 || env->n_pc > 0)
             hipLaunchKernelGGL((att_head_kernel<R, true>), dim3(grid), dim3(kAttBlock), 0, st, starts, goals, n_edges,

@@ -74,8 +74,7 @@ hipError_t vgpu_launch_panda_validate_head_att(const float* starts, const float*
 {
     const size_t threads = n_edges * 8;
     const unsigned grid = (unsigned)((threads + vgpu::kBlock - 1) / vgpu::kBlock);
-    hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-    if (err != hipSuccess) return err;
+    // cnt[n_edges] is written by item_total_kernel, which runs before the count scan
     if (has_ext(env))
         hipLaunchKernelGGL(vgpu::panda_validate_head_att_kernel<true>, dim3(grid), dim3(vgpu::kBlock), 0, st, starts,
                            goals, n_edges, *env, bx, by, bz, ok, n_blocks, cnt);

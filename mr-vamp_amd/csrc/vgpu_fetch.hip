@@ -162,8 +162,8 @@ hipError_t vgpu_launch_fetch_validate_head(const float* starts, const float* goa
                                            const EnvView* env, uint8_t* ok, int32_t* n_blocks, uint32_t* cnt,
                                            hipStream_t st)
 {
-    hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-    if (err != hipSuccess || n_edges == 0) return err;
+    // cnt[n_edges] is written by item_total_kernel, which runs before the count scan
+    if (n_edges == 0) return hipSuccess;
     const unsigned grid = fetch_grid(n_edges * 8);
     if (fetch_has_ext(env))
         hipLaunchKernelGGL(vgpu::fetch_validate_head_kernel<true>, dim3(grid), dim3(vgpu::kFetchBlock), 0, st, starts,

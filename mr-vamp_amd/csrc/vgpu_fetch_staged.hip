@@ -96,18 +96,27 @@ struct FetchR {
 };
 
 #if VGPU_FETCH_PART == 0
+}  // namespace vgpu
+#include "vgpu_lean.hh"
+namespace vgpu {
+// back-step counts with their 64-bit total and the scan's last input (item_total_block), grid-stride
 __global__ __launch_bounds__(kStagedBlock) void fetch_tail_counts_kernel(const float* __restrict__ starts,
                                                                          const float* __restrict__ goals,
                                                                          size_t n_edges,
                                                                          const uint8_t* __restrict__ ok,
                                                                          int32_t* __restrict__ n_blocks,
-                                                                         uint32_t* __restrict__ cnt)
+                                                                         uint32_t* __restrict__ cnt, ItemTotalArgs tot)
 {
-    const size_t e = (size_t)blockIdx.x * kStagedBlock + threadIdx.x;
-    if (e >= n_edges) return;
-    const RakeD<8> rk = rake_setup_d<8, FetchR::kRes>(starts + 8 * e, goals + 8 * e);
-    if (n_blocks) n_blocks[e] = rk.n;
-    cnt[e] = (ok[e] && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;
+    unsigned long long sum = 0;
+    for (size_t e = (size_t)blockIdx.x * kStagedBlock + threadIdx.x; e < n_edges;
+         e += (size_t)gridDim.x * kStagedBlock) {
+        const RakeD<8> rk = rake_setup_d<8, FetchR::kRes>(starts + 8 * e, goals + 8 * e);
+        if (n_blocks) n_blocks[e] = rk.n;
+        const uint32_t c = (ok[e] && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;
+        cnt[e] = c;
+        sum += c;
+    }
+    item_total_block<kStagedBlock>(sum, cnt, n_edges, tot);
 }
 
 #endif
@@ -154,13 +163,13 @@ extern "C" int vgpu_fetch_hitstats(unsigned int* out, int reset)
 
 extern "C" hipError_t vgpu_launch_fetch_tail_counts(const float* starts, const float* goals, size_t n_edges,
                                                     const uint8_t* ok, int32_t* n_blocks, uint32_t* cnt,
-                                                    hipStream_t st)
+                                                    const ItemTotalArgs* tot, hipStream_t st)
 {
-    hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-    if (err != hipSuccess || n_edges == 0) return err;
-    const unsigned grid = (unsigned)((n_edges + vgpu::kStagedBlock - 1) / vgpu::kStagedBlock);
+    if (n_edges == 0) return hipSuccess;
+    const size_t want = (n_edges + vgpu::kStagedBlock - 1) / vgpu::kStagedBlock;
+    const unsigned grid = (unsigned)(want < kTailCountBlocks ? want : kTailCountBlocks);
     hipLaunchKernelGGL(vgpu::fetch_tail_counts_kernel, dim3(grid), dim3(vgpu::kStagedBlock), 0, st, starts, goals,
-                       n_edges, ok, n_blocks, cnt);
+                       n_edges, ok, n_blocks, cnt, *tot);
     return hipGetLastError();
 }
 #endif

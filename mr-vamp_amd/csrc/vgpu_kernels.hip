@@ -21,7 +21,9 @@
 // nothing is a dense contraction worth MFMA (DESIGN.md "Why no MFMA").
 #include <hipcub/hipcub.hpp>
 
+#include "vgpu_lean.hh"
 #include "vgpu_panda.hh"
+#include "vgpu_staged.hh"
 
 namespace vgpu {
 
@@ -137,22 +139,117 @@ __global__ __launch_bounds__(kBlock, VGPU_WAVES_PER_EU) void panda_validate_tail
     if (lane == 0 && !valid) ok[e] = 0;  // every writer stores 0: the race is benign
 }
 
-// 64-bit total of the per-edge back-step counts: the item scan is 32-bit, so a batch whose blocks
-// exceed 2^32 must be rejected before its offsets are trusted (one atomic per wave)
-__global__ __launch_bounds__(kBlock) void total64_kernel(const uint32_t* __restrict__ cnt, size_t n,
-                                                         unsigned long long* __restrict__ out)
+// 64-bit total of the per-edge back-step counts after a MONOLITHIC head kernel (the staged pipelines' tail_counts
+// kernels sum while they count, vgpu_lean.hh item_total_block): the item scan is 32-bit, so a batch whose blocks
+// exceed 2^32 must be rejected before its offsets are trusted.
+__global__ __launch_bounds__(kBlock) void item_total_kernel(uint32_t* __restrict__ cnt, size_t n, ItemTotalArgs t)
 {
     unsigned long long s = 0;
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) s += cnt[i];
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-    // one atomic per block: same-address atomics serialise in L2 (4096 of them took ~50 us)
-    __shared__ unsigned long long part[kBlock / 64];
-    if (__lane_id() == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
+    item_total_block<kBlock>(s, cnt, n, t);
+}
+
+// The scan of a staged pass's per-(check, block) counts (vgpu_staged.hh count_kernel: counts[c * nb + block]):
+// one block per check scans its nb counts into offs, RELATIVE to the check's first block -- queue_kernel uses
+// only offs[c * nb + block] - offs[c * nb] and the plan only the per-check totals, so no scan across checks,
+// no sentinel and no scan workspace.  Tiles of kScanTile counts with a carried prefix, any nb.
+// The block whose ticket comes last (the ticket word is zero between launches: that block resets it)
+//   - stores the per-check totals into the pinned host array host_fired (when given: the pass's read-back is
+//     then a synchronisation, no copy command),
+//   - writes bnd[0 .. checks]: their running sum, the segment boundaries plan_kernel reads (stride 1),
+//   - lays out the round's plan when the round's check set is known at launch (plan != NULL): what
+//     plan_kernel<R, EXT> computes, from the same class table (cls.of[c] = ChildClassesE<R, EXT>::of(c)).
+// Not a template: a kernel templated on the robot alone is one symbol across a robot's part translation units
+// (vgpu_staged.hip kClasses).
+constexpr int kScanTile = 1024;
+__global__ __launch_bounds__(kScanTile) void staged_scan_kernel(const uint32_t* __restrict__ counts,
+                                                                uint32_t* __restrict__ offs, uint32_t nb,
+                                                                uint32_t checks, uint32_t* __restrict__ fired,
+                                                                uint32_t* __restrict__ bnd,
+                                                                uint32_t* __restrict__ ticket,
+                                                                uint32_t* __restrict__ host_fired,
+                                                                StagedPlan* __restrict__ plan, StagedClassTable cls,
+                                                                uint64_t set, uint32_t W, uint32_t n_groups)
+{
+    constexpr int kWaves = kScanTile / 64;
+    __shared__ uint32_t wsum[2][kWaves];
+    __shared__ uint32_t tot[kPlanMaxChecks], pad[kPlanMaxChecks];
+    __shared__ uint32_t is_last;
+    const uint32_t c = blockIdx.x;
+    const uint32_t* __restrict__ in = counts + (size_t)c * nb;
+    uint32_t* __restrict__ out = offs + (size_t)c * nb;
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    uint32_t carry = 0;  // block-uniform: the counts of the tiles before this one
+    uint32_t next = threadIdx.x < nb ? in[threadIdx.x] : 0u;
+    for (uint32_t base = 0, buf = 0; base < nb; base += kScanTile, buf ^= 1u) {
+        const uint32_t i = base + threadIdx.x;  // nb < 2^23 (n_groups < 2^31): no wrap
+        const uint32_t x = next;
+        next = (i + kScanTile < nb) ? in[i + kScanTile] : 0u;  // the next tile's load overlaps this tile's scan
+        uint32_t s = x;  // inclusive scan within the wave
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t t = __shfl_up(s, d);
+            if (lane >= d) s += t;
+        }
+        if (lane == 63) wsum[buf][w] = s;
+        __syncthreads();  // one barrier per tile: the next tile writes the other buffer
+        uint32_t pre = 0, all = 0;
+        for (int k = 0; k < kWaves; ++k) {
+            const uint32_t v = wsum[buf][k];
+            pre += (k < w) ? v : 0u;
+            all += v;
+        }
+        if (i < nb) out[i] = carry + pre + s - x;
+        carry += all;
+    }
     if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kBlock / 64; ++w) t += part[w];
-        if (t) atomicAdd(out, t);
+        // the total leaves this thread (write-through store, drained) before its ticket is taken; the last ticket
+        // holder reads the totals past its L1 (agent-scope loads)
+        __hip_atomic_store(fired + c, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        is_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == checks - 1u;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    if (threadIdx.x < kPlanMaxChecks) {
+        const bool have = threadIdx.x < checks;
+        const uint32_t f = have ? __hip_atomic_load(fired + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        const bool on = have && ((set >> threadIdx.x) & 1u);
+        tot[threadIdx.x] = f;
+        pad[threadIdx.x] = on ? (f + W - 1) / W * W : 0u;  // the check's segment, padded to whole waves
+        if (have && host_fired) host_fired[threadIdx.x] = f;
+    }
+    __syncthreads();
+    if (threadIdx.x > kPlanMaxChecks) return;  // lane checks (<= 64) writes the last boundary
+    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // one lane per check: its boundary (checks in order) and its segment start (class-major, then in order);
+    // lanes 0 .. kPlanMaxClasses - 1 also sum their class's range
+    const uint32_t k = threadIdx.x;
+    const uint32_t my_cls = k < checks ? cls.of[k] : 0xFFu;
+    uint32_t before = 0, start = 0, lo = 0, hi = 0;
+    for (uint32_t j = 0; j < checks; ++j) {
+        const uint32_t cj = cls.of[j], pj = pad[j];
+        before += (j < k) ? tot[j] : 0u;
+        start += (cj < my_cls || (cj == my_cls && j < k)) ? pj : 0u;
+        lo += (cj < k) ? pj : 0u;
+        hi += (cj <= k) ? pj : 0u;
+    }
+    if (k <= checks) bnd[k] = before;
+    if (!plan) return;
+    if (k < checks) {  // what plan_kernel<R, EXT> lays out
+        const bool on = (set >> k) & 1u;
+        plan->start[k] = start;
+        plan->fill[k] = start + (on ? tot[k] : 0u);
+        plan->end[k] = start + pad[k];
+    }
+    if (k < (uint32_t)kPlanMaxClasses) {  // classes the robot does not have stay empty
+        plan->lo[k] = lo;
+        plan->hi[k] = hi;
+    }
+    if (k == 0) {
+        uint32_t total = 0;
+        for (uint32_t j = 0; j < checks; ++j) total += pad[j];
+        plan->total = total;
+        plan->n_groups = n_groups;
     }
 }
 
@@ -245,8 +342,6 @@ hipError_t vgpu_launch_panda_validate_head(const float* starts, const float* goa
 {
     const size_t threads = n_edges * 8;
     const unsigned grid = (unsigned)((threads + vgpu::kBlock - 1) / vgpu::kBlock);
-    hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-    if (err != hipSuccess) return err;
     if (has_ext(env))
         hipLaunchKernelGGL(vgpu::panda_validate_head_kernel<true>, dim3(grid), dim3(vgpu::kBlock), 0, st, starts,
                            goals, n_edges, *env, bx, by, bz, ok, n_blocks, cnt);
@@ -256,13 +351,24 @@ hipError_t vgpu_launch_panda_validate_head(const float* starts, const float* goa
     return hipGetLastError();
 }
 
-hipError_t vgpu_launch_total64(const uint32_t* cnt, size_t n, unsigned long long* out, hipStream_t st)
+hipError_t vgpu_launch_item_total(uint32_t* cnt, size_t n, const ItemTotalArgs* t, hipStream_t st)
 {
-    hipError_t err = hipMemsetAsync(out, 0, sizeof(unsigned long long), st);
-    if (err != hipSuccess || n == 0) return err;
     const size_t want = (n + vgpu::kBlock - 1) / vgpu::kBlock;
-    const unsigned grid = (unsigned)(want < 256 ? want : 256);
-    hipLaunchKernelGGL(vgpu::total64_kernel, dim3(grid), dim3(vgpu::kBlock), 0, st, cnt, n, out);
+    const unsigned grid = (unsigned)(want < 256 ? (want ? want : 1) : 256);
+    hipLaunchKernelGGL(vgpu::item_total_kernel, dim3(grid), dim3(vgpu::kBlock), 0, st, cnt, n, *t);
+    return hipGetLastError();
+}
+
+// plan = NULL: the totals and boundaries only (the round's check set is chosen from them on the host)
+hipError_t vgpu_launch_staged_scan(const uint32_t* counts, uint32_t* offs, uint32_t nb, int checks, uint32_t* fired,
+                                   uint32_t* bnd, uint32_t* ticket, uint32_t* host_fired, void* plan,
+                                   const StagedClassTable* cls, uint64_t set, uint32_t W, uint32_t n_groups,
+                                   hipStream_t st)
+{
+    if (checks < 1 || checks > vgpu::kPlanMaxChecks || nb == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(vgpu::staged_scan_kernel, dim3((unsigned)checks), dim3(vgpu::kScanTile), 0, st, counts, offs,
+                       nb, (uint32_t)checks, fired, bnd, ticket, host_fired, (vgpu::StagedPlan*)plan, *cls, set, W,
+                       n_groups);
     return hipGetLastError();
 }
 

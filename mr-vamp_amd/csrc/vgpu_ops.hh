@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "vgpu_lean.hh"
+
 struct EnvView;
 
 struct RobotOps {
@@ -20,5 +22,5 @@ struct RobotOps {
     hipError_t (*validate_tail)(const float* starts, const float* goals, size_t n_items, const EnvView* env,
                                 uint8_t* ok, const uint32_t* off, const uint32_t* item_edge, hipStream_t st);
     hipError_t (*tail_counts)(const float* starts, const float* goals, size_t n_edges, const uint8_t* ok,
-                              int32_t* n_blocks, uint32_t* cnt, hipStream_t st);
+                              int32_t* n_blocks, uint32_t* cnt, const ItemTotalArgs* tot, hipStream_t st);
 };

@@ -115,8 +115,8 @@ hipError_t vgpu_launch_pair_validate_head(const float* starts, const float* goal
                                           const float base[6], uint8_t* ok, int32_t* n_blocks, uint32_t* cnt,
                                           hipStream_t st)
 {
-    hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-    if (err != hipSuccess || n_edges == 0) return err;
+    // cnt[n_edges] is written by item_total_kernel, which runs before the count scan
+    if (n_edges == 0) return hipSuccess;
     const vgpu::PairBase pb{base[0], base[1], base[2], base[3], base[4], base[5]};
     const unsigned grid = pair_grid(n_edges * 8);
     if (pair_has_ext(env))

@@ -164,31 +164,39 @@ static_assert(panda_pair_n_checks <= 2 * panda_pair_chunk, "two inter-arm chunks
 #if VGPU_PAIR_PASS == 0
 VGPU_STAGED_EXPORTS(vgpu::PairArmR<0>, pair_a)
 
+#include "vgpu_lean.hh"
 namespace vgpu {
-// validate head -> tail back-step counts of the 14-dof rake
+// validate head -> tail back-step counts of the 14-dof rake, with their 64-bit total and the scan's last input
+// (item_total_block); grid-stride over the edges
 __global__ __launch_bounds__(kStagedBlock) void pair_tail_counts_kernel(const float* __restrict__ starts,
                                                                         const float* __restrict__ goals,
                                                                         size_t n_edges, const uint8_t* __restrict__ ok,
                                                                         int32_t* __restrict__ n_blocks,
-                                                                        uint32_t* __restrict__ cnt)
+                                                                        uint32_t* __restrict__ cnt, ItemTotalArgs tot)
 {
-    const size_t e = (size_t)blockIdx.x * kStagedBlock + threadIdx.x;
-    if (e >= n_edges) return;
-    const RakeD<kPairDimS> rk = rake_setup_d<kPairDimS, kPairResS>(starts + kPairDimS * e, goals + kPairDimS * e);
-    if (n_blocks) n_blocks[e] = rk.n;
-    cnt[e] = ((!ok || ok[e]) && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;
+    unsigned long long sum = 0;
+    for (size_t e = (size_t)blockIdx.x * kStagedBlock + threadIdx.x; e < n_edges;
+         e += (size_t)gridDim.x * kStagedBlock) {
+        const RakeD<kPairDimS> rk = rake_setup_d<kPairDimS, kPairResS>(starts + kPairDimS * e, goals + kPairDimS * e);
+        if (n_blocks) n_blocks[e] = rk.n;
+        const uint32_t c = ((!ok || ok[e]) && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;
+        cnt[e] = c;
+        sum += c;
+    }
+    item_total_block<kStagedBlock>(sum, cnt, n_edges, tot);
 }
 
 }  // namespace vgpu
 
 extern "C" hipError_t vgpu_launch_pair_tail_counts(const float* starts, const float* goals, size_t n_edges,
-                                                   const uint8_t* ok, int32_t* n_blocks, uint32_t* cnt, hipStream_t st)
+                                                   const uint8_t* ok, int32_t* n_blocks, uint32_t* cnt,
+                                                   const ItemTotalArgs* tot, hipStream_t st)
 {
-    hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-    if (err != hipSuccess || n_edges == 0) return err;
-    const unsigned grid = (unsigned)((n_edges + vgpu::kStagedBlock - 1) / vgpu::kStagedBlock);
+    if (n_edges == 0) return hipSuccess;
+    const size_t want = (n_edges + vgpu::kStagedBlock - 1) / vgpu::kStagedBlock;
+    const unsigned grid = (unsigned)(want < kTailCountBlocks ? want : kTailCountBlocks);
     hipLaunchKernelGGL(vgpu::pair_tail_counts_kernel, dim3(grid), dim3(vgpu::kStagedBlock), 0, st, starts, goals,
-                       n_edges, ok, n_blocks, cnt);
+                       n_edges, ok, n_blocks, cnt, *tot);
     return hipGetLastError();
 }
 #elif VGPU_PAIR_PASS == 1

@@ -112,13 +112,18 @@ __global__ __launch_bounds__(kRobotBlock) void robot_tail_counts_kernel(const fl
                                                                         const float* __restrict__ goals, size_t n_edges,
                                                                         const uint8_t* __restrict__ ok,
                                                                         int32_t* __restrict__ n_blocks,
-                                                                        uint32_t* __restrict__ cnt)
+                                                                        uint32_t* __restrict__ cnt, ItemTotalArgs tot)
 {
-    const size_t e = (size_t)blockIdx.x * kRobotBlock + threadIdx.x;
-    if (e >= n_edges) return;
-    const RakeD<R::D> rk = rake_setup_d<R::D, R::kRes>(starts + R::D * e, goals + R::D * e);
-    if (n_blocks) n_blocks[e] = rk.n;
-    cnt[e] = (ok[e] && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;
+    // grid-stride; the counts' 64-bit total and the scan's last input: vgpu_lean.hh item_total_block
+    unsigned long long sum = 0;
+    for (size_t e = (size_t)blockIdx.x * kRobotBlock + threadIdx.x; e < n_edges; e += (size_t)gridDim.x * kRobotBlock) {
+        const RakeD<R::D> rk = rake_setup_d<R::D, R::kRes>(starts + R::D * e, goals + R::D * e);
+        if (n_blocks) n_blocks[e] = rk.n;
+        const uint32_t c = (ok[e] && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;
+        cnt[e] = c;
+        sum += c;
+    }
+    item_total_block<kRobotBlock>(sum, cnt, n_edges, tot);
 }
 
 template <class R>
@@ -163,8 +168,7 @@ struct RobotHost {
     static hipError_t validate_head(const float* s, const float* g, size_t n_edges, const EnvView* env, uint8_t* ok,
                                     int32_t* n_blocks, uint32_t* cnt, hipStream_t st)
     {
-        hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-        if (err != hipSuccess || n_edges == 0) return err;
+        if (n_edges == 0) return hipSuccess;  // cnt[n_edges]: written by item_total_kernel, which runs before the scan
         if (ext(env))
             hipLaunchKernelGGL((robot_validate_head_kernel<R, true>), dim3(grid(n_edges * 8)), dim3(kRobotBlock), 0, st,
                                s, g, n_edges, *env, ok, n_blocks, cnt);
@@ -186,12 +190,12 @@ struct RobotHost {
         return hipGetLastError();
     }
     static hipError_t tail_counts(const float* s, const float* g, size_t n_edges, const uint8_t* ok, int32_t* n_blocks,
-                                  uint32_t* cnt, hipStream_t st)
+                                  uint32_t* cnt, const ItemTotalArgs* tot, hipStream_t st)
     {
-        hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-        if (err != hipSuccess || n_edges == 0) return err;
-        hipLaunchKernelGGL((robot_tail_counts_kernel<R>), dim3(grid(n_edges)), dim3(kRobotBlock), 0, st, s, g, n_edges,
-                           ok, n_blocks, cnt);
+        if (n_edges == 0) return hipSuccess;
+        const unsigned blocks = grid(n_edges) < kTailCountBlocks ? grid(n_edges) : kTailCountBlocks;
+        hipLaunchKernelGGL((robot_tail_counts_kernel<R>), dim3(blocks), dim3(kRobotBlock), 0, st, s, g, n_edges, ok,
+                           n_blocks, cnt, *tot);
         return hipGetLastError();
     }
 };

@@ -35,8 +35,9 @@ namespace vgpu {
 
 constexpr int kStagedBlock = 256;
 
-// The device-side segment layout of one round of a staged pass (written by plan_kernel after the
-// round's count + scan): each check's item segment [start, end) (wave-aligned; items [fill, end)
+// The device-side segment layout of one round of a staged pass (written by the last block of the
+// round's scan, vgpu_kernels.hip staged_scan_kernel, or by plan_kernel for a first round whose check set
+// the host picks from the totals): each check's item segment [start, end) (wave-aligned; items [fill, end)
 // are padding), laid out class-major so each children class covers one contiguous range [lo, hi).
 // The host reads only the FIRST round's per-check counts back (one sync per pass): they bound
 // every later round's counts, which sizes every children grid without another read-back.
@@ -466,7 +467,8 @@ __global__ __launch_bounds__(kStagedBlock, (LeadWaves<R, Src>::v)) void lead_ker
 // an earlier round contributes no work to later ones, which recovers the reference's early exit.
 // count and queue run one thread per GROUP (not per lane: they only read the group's mask and
 // flag), kStagedBlock groups per block; per-(check, block) counts are stored check-major,
-// counts[c * blocks + block], for one flat exclusive scan.
+// counts[c * blocks + block], and scanned per check (staged_scan_kernel: offs is relative to the check's
+// first block, offs[c * blocks] = 0).
 template <class R, class Src>
 __device__ __forceinline__ typename R::Mask round_bits(const Src& src, const typename R::Mask* __restrict__ mask,
                                                        uint32_t n_groups, typename R::Mask set,
@@ -487,8 +489,10 @@ __global__ __launch_bounds__(kStagedBlock) void count_kernel(Src src, const type
     block_counts<R>(round_bits<R>(src, mask, n_groups, set, valid, g), counts);
 }
 
-// After a round's count + scan: fired[c] = offs[(c+1)*nb] - offs[c*nb]; the round's segments,
-// class-major.  One lane per check computes its fired count, lane 0 lays them out.
+// The plan of a first round whose check set the host chose after the scan (every other round's plan comes
+// out of staged_scan_kernel): fired[c] = offs[(c+1)*nb] - offs[c*nb] over the boundaries the scan left
+// (its bnd array, nb = 1); the round's segments, class-major.  One lane per check computes its fired
+// count, lane 0 lays them out.
 template <class R, bool EXT>
 __global__ __launch_bounds__(64) void plan_kernel(const uint32_t* __restrict__ offs, uint32_t nb, uint32_t W,
                                                   uint64_t set, uint32_t n_groups, StagedPlan* __restrict__ plan)
@@ -518,7 +522,7 @@ __global__ __launch_bounds__(64) void plan_kernel(const uint32_t* __restrict__ o
 
 // Position of group g in check c's segment:
 //   start[c] + (offs[c*nb + block] - offs[c*nb]) + rank of g among the block's groups with bit c
-// -- ascending group order within each segment, no atomics.
+// -- ascending group order within each segment, no atomics (offs[c*nb] is 0 under the per-check scan).
 template <class R, class Src>
 __global__ __launch_bounds__(kStagedBlock) void queue_kernel(Src src, const typename R::Mask* __restrict__ mask,
                                                              uint32_t n_groups, typename R::Mask set,

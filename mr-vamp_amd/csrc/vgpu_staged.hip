@@ -119,18 +119,26 @@ struct PandaR {
 };
 
 #if VGPU_PANDA_PART == 0
-// validate head -> tail: back-step items for edges still valid after block 0
+}  // namespace vgpu
+#include "vgpu_lean.hh"
+namespace vgpu {
+// validate head -> tail: back-step items for edges still valid after block 0, their 64-bit total and the count
+// scan's last input (item_total_block); grid-stride over the edges, at most kTailCountBlocks blocks
 __global__ __launch_bounds__(kBlock) void tail_counts_kernel(const float* __restrict__ starts,
                                                              const float* __restrict__ goals, size_t n_edges,
                                                              const uint8_t* __restrict__ ok,
                                                              int32_t* __restrict__ n_blocks,
-                                                             uint32_t* __restrict__ cnt)
+                                                             uint32_t* __restrict__ cnt, ItemTotalArgs tot)
 {
-    const size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (e >= n_edges) return;
-    const Rake rk = rake_setup(starts + 7 * e, goals + 7 * e);
-    if (n_blocks) n_blocks[e] = rk.n;
-    cnt[e] = ((!ok || ok[e]) && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;  // ok = NULL: every back-step (full mask)
+    unsigned long long sum = 0;
+    for (size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x; e < n_edges; e += (size_t)gridDim.x * kBlock) {
+        const Rake rk = rake_setup(starts + 7 * e, goals + 7 * e);
+        if (n_blocks) n_blocks[e] = rk.n;
+        const uint32_t c = ((!ok || ok[e]) && rk.n > 1) ? (uint32_t)(rk.n - 1) : 0u;  // ok = NULL: every back-step (full mask)
+        cnt[e] = c;
+        sum += c;
+    }
+    item_total_block<kBlock>(sum, cnt, n_edges, tot);
 }
 
 // full-mask mode: edge e's blocks at off[e] + e .. (+ n_e - 1); block 0 is the head's result, and the
@@ -180,13 +188,14 @@ extern "C" hipError_t vgpu_launch_mask_finish(size_t n_edges, const uint32_t* of
 }
 
 extern "C" hipError_t vgpu_launch_tail_counts(const float* starts, const float* goals, size_t n_edges,
-                                              const uint8_t* ok, int32_t* n_blocks, uint32_t* cnt, hipStream_t st)
+                                              const uint8_t* ok, int32_t* n_blocks, uint32_t* cnt,
+                                              const ItemTotalArgs* tot, hipStream_t st)
 {
-    hipError_t err = hipMemsetAsync(cnt + n_edges, 0, sizeof(uint32_t), st);
-    if (err != hipSuccess || n_edges == 0) return err;
-    const unsigned grid = (unsigned)((n_edges + vgpu::kBlock - 1) / vgpu::kBlock);
+    if (n_edges == 0) return hipSuccess;
+    const size_t want = (n_edges + vgpu::kBlock - 1) / vgpu::kBlock;
+    const unsigned grid = (unsigned)(want < kTailCountBlocks ? want : kTailCountBlocks);
     hipLaunchKernelGGL(vgpu::tail_counts_kernel, dim3(grid), dim3(vgpu::kBlock), 0, st, starts, goals, n_edges, ok,
-                       n_blocks, cnt);
+                       n_blocks, cnt, *tot);
     return hipGetLastError();
 }
 
