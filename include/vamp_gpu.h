@@ -345,6 +345,52 @@ int vgpu_cpu_rrtc(const vgpu_robot *robot, vgpu_env *env, const float *start, co
                   const vgpu_rrtc_settings *settings, uint64_t *rng_index, float *path, size_t path_cap,
                   vgpu_plan_result *result);
 
+/* ---- path simplification (planning/simplify.hh:192-260) ------------------------------------------ */
+/* vamp::planning::SimplifyRoutine (planning/simplify_settings.hh:7-13) */
+enum { VGPU_SIMPLIFY_BSPLINE = 0, VGPU_SIMPLIFY_REDUCE = 1, VGPU_SIMPLIFY_SHORTCUT = 2, VGPU_SIMPLIFY_PERTURB = 3 };
+/* per-path outcome: DONE = the reference's result; CAPACITY = the path stopped before a B-spline subdivide
+ * that would have exceeded the length limit (waypoints as before that subdivide, iterations as counted) */
+enum { VGPU_SIMPLIFY_DONE = 0, VGPU_SIMPLIFY_CAPACITY = 1 };
+/* vamp::planning::SimplifySettings (planning/simplify_settings.hh:41-51) with its defaults.  Supported
+ * operations: SHORTCUT and BSPLINE (both deterministic).  REDUCE and PERTURB draw from the reference's
+ * mt19937 distribution and `interpolate` != 0 resamples the path first: VGPU_ERR_UNSUPPORTED. */
+typedef struct vgpu_simplify_settings {
+    uint64_t max_iterations;                 /* 5 */
+    uint64_t interpolate;                    /* 0; non-zero: VGPU_ERR_UNSUPPORTED */
+    int32_t n_operations, operations[8];     /* {SHORTCUT, BSPLINE} */
+    uint64_t bspline_max_steps;              /* 1 */
+    float bspline_min_change;                /* 0.1 */
+    float bspline_midpoint_interpolation;    /* 0.5 */
+    uint64_t max_path_len;                   /* extension: 0 = unlimited (CPU) / the buffer's cap (GPU) */
+} vgpu_simplify_settings;
+int vgpu_simplify_settings_default(vgpu_simplify_settings *s);
+/* simplify<Robot, 8, Robot::resolution>(path, env, settings, rng) on the CPU rake: path[len][dim] ->
+ * out[result->path_len][dim]; result->iterations, cost (Path::cost of the result, plan.hh:13-32) and
+ * nanoseconds are set, solved = 1, size[0] = validate_motion calls made (an extension: the reference leaves
+ * size empty), size[1] = 0.  *status (optional) = VGPU_SIMPLIFY_*.  If out_cap <
+ * result->path_len the call returns VGPU_ERR_INVALID_ARG with path_len set (as vgpu_cpu_rrtc's path_cap). */
+int vgpu_cpu_simplify(const vgpu_robot *robot, vgpu_env *env, const float *path, size_t len,
+                      const vgpu_simplify_settings *settings, float *out, size_t out_cap, vgpu_plan_result *result,
+                      int32_t *status);
+/* The same for n_paths paths in one environment, in lockstep on the GPU (mr-vamp_amd/csrc/vgpu_simplify.hip):
+ * every round gathers the candidate edges of all paths still working (one shortcut row, or the two edges of
+ * every B-spline midpoint that moved more than min_change) into one vgpu_validate_motions call, and resolves
+ * them on the device; each path's result equals vgpu_cpu_simplify's bit for bit.  Device pointers:
+ * waypoints[n_paths][cap][dim] and len[n_paths] in and out (len[p] <= cap; a longer one is left alone with
+ * status CAPACITY), iterations[n_paths], status[n_paths], cost[n_paths] out (any of the three may be NULL).
+ * The length limit of a path is min(cap, max_path_len) (max_path_len 0: cap).  n_paths * cap < 2^31.
+ * Synchronises once per round on top of the validate call's own read-backs. */
+int vgpu_simplify_paths(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *env, float *waypoints, size_t cap,
+                        uint32_t *len, size_t n_paths, const vgpu_simplify_settings *settings, uint32_t *iterations,
+                        uint8_t *status, float *cost);
+/* host pointers: copy in, run, copy out, synchronise */
+int vgpu_simplify_paths_host(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *env, float *waypoints, size_t cap,
+                             uint32_t *len, size_t n_paths, const vgpu_simplify_settings *settings,
+                             uint32_t *iterations, uint8_t *status, float *cost);
+/* counters of the context's last vgpu_simplify_paths call: out[0] rounds, out[1] validate calls, out[2] edges
+ * validated */
+int vgpu_simplify_stats(const vgpu_ctx *ctx, uint64_t out[3]);
+
 /* build_roadmap's neighbour queries on the host CPU (the reference's nigh KD-tree role, planning/nn.hh:89-95;
  * mr-vamp_amd/csrc/cpu/vcpu_roadmap.cpp): an exact static k-d tree over V[n][dim] with per-subtree minimum
  * vertex indices, answering the causal query of each listed vertex q = queries[j] (the k[q] nearest of

@@ -26,6 +26,7 @@
 #include "vgpu_host_env.hh"
 #include "vgpu_lean.hh"
 #include "vgpu_ops.hh"
+#include "vgpu_simplify.hh"
 #include "gen/radii.inc"
 
 extern "C" {
@@ -288,6 +289,11 @@ struct vgpu_ctx {
     float* small = nullptr;
     // debug-check words of the kernels without an environment (kNN index): VGPU_DCHECK, make DEBUG=1
     uint32_t* dbg = nullptr;
+    // batched simplify (vgpu_simplify.hip): workspace, the pinned round totals, the last call's counters
+    void* simp = nullptr;
+    size_t simp_bytes = 0;
+    uint32_t* simp_host = nullptr;
+    uint64_t simp_stats[3] = {0, 0, 0};
     // optional phase timing
     bool prof = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -448,6 +454,8 @@ extern "C" void vgpu_ctx_destroy(vgpu_ctx* c)
     if (c->knn_idx) (void)hipFree(c->knn_idx);
     if (c->small) (void)hipFree(c->small);
     if (c->dbg) (void)hipFree(c->dbg);
+    if (c->simp) (void)hipFree(c->simp);
+    if (c->simp_host) (void)hipHostFree(c->simp_host);
     if (c->tick) (void)hipFree(c->tick);
     if (c->total_host) (void)hipHostFree(c->total_host);
     for (auto& ev : c->ev)
@@ -2503,6 +2511,132 @@ try {
     if ((rc = vgpu_compact(c, (const float*)d, keep, n, 3, (float*)(d + pb + kb), (uint32_t*)(d + 2 * pb + kb), count)))
         return rc;
     HIPCHK(c, hipMemcpyAsync(out, d + pb + kb, *count * 12, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipStreamSynchronize(c->cur));
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+// ---- batched path simplification (planning/simplify.hh:192-260; kernels in vgpu_simplify.hip) ------------------
+namespace vcpu {
+int simplify_settings_check(const vgpu_simplify_settings* s, const char** field);  // cpu/vcpu_simplify.cpp
+}
+
+// Rounds until no path is working: prepare (per-path edge counts; a B-spline step subdivides and picks its
+// candidates) + scan, ONE read-back of {edges, paths working}, then -- when there are edges -- emit, one
+// vgpu_validate_motions over the compact list, and resolve, which advances every path's control state.
+extern "C" int vgpu_simplify_paths(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, float* waypoints, size_t cap,
+                                   uint32_t* len, size_t n_paths, const vgpu_simplify_settings* settings,
+                                   uint32_t* iterations, uint8_t* status, float* cost)
+try {
+    if (!c || !e || e->ctx != c) return fail(c, VGPU_ERR_INVALID_ARG, "bad context/environment");
+    float b[3];
+    int rc = check_robot(c, r, b);
+    if (rc) return rc;
+    const char* field;
+    if ((rc = vcpu::simplify_settings_check(settings, &field))) {
+        c->err = std::string(rc == VGPU_ERR_UNSUPPORTED ? "simplify: not supported: " : "simplify: bad ") + field;
+        return rc;
+    }
+    if (e->attached && r->kind == VGPU_ROBOT_PANDA_PAIR)
+        return fail(c, VGPU_ERR_UNSUPPORTED, "attachments: no fkcc_attach for the composite");
+    c->simp_stats[0] = c->simp_stats[1] = c->simp_stats[2] = 0;
+    if (n_paths == 0) return VGPU_OK;
+    if (!waypoints || !len || cap == 0) return fail(c, VGPU_ERR_INVALID_ARG, "null buffers or zero capacity");
+    if (n_paths >= ((size_t)1 << 31) || cap >= ((size_t)1 << 31) || n_paths * cap >= ((size_t)1 << 31))
+        return fail(c, VGPU_ERR_INVALID_ARG, "n_paths * cap must be below 2^31 (split the batch)");
+    const size_t dim = dim_of(r), slots = n_paths * cap;
+    HIPCHK(c, ctx_device(c));
+    const size_t wb = al(slots * dim * 4), okb = al(slots), cb = al(slots * 4),
+                 sb = al(n_paths * vgpu::kSimplifyWords * 4), ib = al((n_paths + 1) * 4);
+    const size_t need = 3 * wb + okb + cb + sb + 2 * ib;
+    if (need > c->simp_bytes) {
+        if (c->simp) {
+            HIPCHK(c, hipStreamSynchronize(c->cur));
+            HIPCHK(c, hipFree(c->simp));
+            c->simp = nullptr;
+            c->simp_bytes = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->simp, need));
+        c->simp_bytes = need;
+    }
+    if (!c->simp_host) HIPCHK(c, hipHostMalloc((void**)&c->simp_host, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    char* p = (char*)c->simp;
+    vgpu::SimplifyArgs a{};
+    a.buf[0] = waypoints;
+    a.buf[1] = (float*)p;
+    a.starts = (float*)(p + wb);
+    a.goals = (float*)(p + 2 * wb);
+    uint8_t* ok = (uint8_t*)(p + 3 * wb);
+    a.ok = ok;
+    a.cand = (uint32_t*)(p + 3 * wb + okb);
+    a.st = (uint32_t*)(p + 3 * wb + okb + cb);
+    a.cnt = (uint32_t*)(p + 3 * wb + okb + cb + sb);
+    a.off = (uint32_t*)(p + 3 * wb + okb + cb + sb + ib);
+    a.len = len;
+    a.host = c->simp_host;
+    a.n_paths = (uint32_t)n_paths;
+    a.cap = (uint32_t)cap;
+    a.limit = (uint32_t)(settings->max_path_len ? std::min<uint64_t>(settings->max_path_len, cap) : cap);
+    a.dim = (uint32_t)dim;
+    a.max_iterations = (uint32_t)std::min<uint64_t>(settings->max_iterations, 0xffffffffu);
+    a.max_steps = (uint32_t)std::min<uint64_t>(settings->bspline_max_steps, 0xffffffffu);
+    a.n_ops = (uint32_t)settings->n_operations;
+    for (uint32_t k = 0; k < a.n_ops; ++k) a.ops[k] = (uint32_t)settings->operations[k];
+    a.min_change = settings->bspline_min_change;
+    a.midpoint = settings->bspline_midpoint_interpolation;
+    HIPCHK(c, vgpu_launch_simplify_init(&a, c->cur));
+    for (;;) {
+        HIPCHK(c, vgpu_launch_simplify_prepare(&a, c->cur));
+        HIPCHK(c, hipStreamSynchronize(c->cur));
+        const uint32_t n_edges = c->simp_host[0], working = c->simp_host[1];
+        if (!working) break;
+        c->simp_stats[0] += 1;
+        if (n_edges > slots) return fail(c, VGPU_ERR_INTERNAL, "simplify: a round's edge list exceeds its workspace");
+        if (n_edges) {
+            HIPCHK(c, vgpu_launch_simplify_emit(&a, c->cur));
+            if ((rc = vgpu_validate_motions(c, r, e, a.starts, a.goals, n_edges, ok, nullptr))) return rc;
+            c->simp_stats[1] += 1;
+            c->simp_stats[2] += n_edges;
+        }
+        HIPCHK(c, vgpu_launch_simplify_resolve(&a, c->cur));
+    }
+    HIPCHK(c, vgpu_launch_simplify_finish(&a, iterations, status, cost, c->cur));
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_simplify_stats(const vgpu_ctx* c, uint64_t out[3])
+try {
+    if (!c || !out) return VGPU_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k) out[k] = c->simp_stats[k];
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_simplify_paths_host(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, float* waypoints, size_t cap,
+                                        uint32_t* len, size_t n_paths, const vgpu_simplify_settings* settings,
+                                        uint32_t* iterations, uint8_t* status, float* cost)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    if (n_paths == 0) return VGPU_OK;
+    if (!waypoints || !len || cap == 0) return fail(c, VGPU_ERR_INVALID_ARG, "null buffers or zero capacity");
+    if (n_paths >= ((size_t)1 << 31) || cap >= ((size_t)1 << 31) || n_paths * cap >= ((size_t)1 << 31))
+        return fail(c, VGPU_ERR_INVALID_ARG, "n_paths * cap must be below 2^31 (split the batch)");
+    char* d;
+    const size_t wbytes = n_paths * cap * dim_of(r) * 4;
+    const size_t wb = al(wbytes), ib = al(n_paths * 4), sb = al(n_paths);
+    int rc = stage(c, wb + 3 * ib + sb, &d);
+    if (rc) return rc;
+    float* wd = (float*)d;
+    uint32_t* ld = (uint32_t*)(d + wb);
+    uint32_t* itd = (uint32_t*)(d + wb + ib);
+    float* cd = (float*)(d + wb + 2 * ib);
+    uint8_t* sd = (uint8_t*)(d + wb + 3 * ib);
+    HIPCHK(c, hipMemcpyAsync(wd, waypoints, wbytes, hipMemcpyHostToDevice, c->cur));
+    HIPCHK(c, hipMemcpyAsync(ld, len, n_paths * 4, hipMemcpyHostToDevice, c->cur));
+    if ((rc = vgpu_simplify_paths(c, r, e, wd, cap, ld, n_paths, settings, itd, sd, cd))) return rc;
+    HIPCHK(c, hipMemcpyAsync(waypoints, wd, wbytes, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipMemcpyAsync(len, ld, n_paths * 4, hipMemcpyDeviceToHost, c->cur));
+    if (iterations) HIPCHK(c, hipMemcpyAsync(iterations, itd, n_paths * 4, hipMemcpyDeviceToHost, c->cur));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, sd, n_paths, hipMemcpyDeviceToHost, c->cur));
+    if (cost) HIPCHK(c, hipMemcpyAsync(cost, cd, n_paths * 4, hipMemcpyDeviceToHost, c->cur));
     HIPCHK(c, hipStreamSynchronize(c->cur));
     return VGPU_OK;
 } VGPU_ABI_CATCH

@@ -25,7 +25,7 @@ from ._lib import VgpuError, check, load
 
 __all__ = [
     "Context", "context", "Environment", "Attachment", "Sphere", "Cuboid", "Cylinder", "HeightField", "make_heightfield", "Robot", "halton", "compact_device",
-    "PandaBase", "panda", "panda_0_0", "VgpuError",
+    "PandaBase", "panda", "panda_0_0", "VgpuError", "SimplifySettings", "SimplifyRoutine", "BSplineSettings",
 ]
 
 
@@ -518,6 +518,57 @@ class RRTCSettings:
                                      int(self.start_tree_first))
 
 
+class SimplifyRoutine:
+    """vamp::planning::SimplifyRoutine (planning/simplify_settings.hh:7-13)."""
+    BSPLINE, REDUCE, SHORTCUT, PERTURB = 0, 1, 2, 3
+
+
+class BSplineSettings:
+    """vamp::planning::BSplineSettings (planning/simplify_settings.hh:15-20)."""
+
+    def __init__(self):
+        self.max_steps = 1
+        self.min_change = 0.1
+        self.midpoint_interpolation = 0.5
+
+
+class SimplifySettings:
+    """vamp::planning::SimplifySettings (planning/simplify_settings.hh:41-51), same field names and defaults:
+    max_iterations, interpolate, operations, bspline.{max_steps, min_change, midpoint_interpolation}.
+    SHORTCUT and BSPLINE are built; REDUCE, PERTURB and a non-zero `interpolate` raise (unsupported).
+    max_path_len is an extension: a path stops before a subdivide that would exceed it (0 = no limit on the
+    CPU, the buffer's capacity in a batch)."""
+
+    def __init__(self, **kw):
+        self.max_iterations = 5
+        self.interpolate = 0
+        self.operations = [SimplifyRoutine.SHORTCUT, SimplifyRoutine.BSPLINE]
+        self.bspline = BSplineSettings()
+        self.max_path_len = 0
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            setattr(self, k, v)
+
+    def c(self) -> _lib.VgpuSimplifySettings:
+        ops = [int(o) for o in self.operations]
+        if len(ops) > 8:
+            raise ValueError("at most 8 operations")
+        return _lib.VgpuSimplifySettings(int(self.max_iterations), int(self.interpolate), len(ops),
+                                         (C.c_int32 * 8)(*ops), int(self.bspline.max_steps),
+                                         float(self.bspline.min_change), float(self.bspline.midpoint_interpolation),
+                                         int(self.max_path_len))
+
+    def unsupported(self) -> Optional[str]:
+        """the field this build does not support, or None"""
+        if self.interpolate:
+            return "interpolate"
+        for o in self.operations:
+            if int(o) in (SimplifyRoutine.REDUCE, SimplifyRoutine.PERTURB):
+                return "operations: " + ("REDUCE" if int(o) == SimplifyRoutine.REDUCE else "PERTURB")
+        return None
+
+
 class Halton:
     """rng::Halton<dim> (random/halton.hh) as the planners consume it: vamp.<robot>.halton() with
     reset() / skip(n) / next(); the state is the 1-based index of the next draw."""
@@ -766,6 +817,88 @@ class Robot:
         return PlanningResult(path[:res.path_len].copy(), float(res.cost), int(res.iterations),
                               (int(res.size[0]), int(res.size[1])), int(res.nanoseconds), bool(res.solved))
 
+    def simplify(self, path, environment: Environment, settings: Optional[SimplifySettings] = None,
+                 rng: Optional[Halton] = None) -> PlanningResult:
+        """vamp.<robot>.simplify(path, environment, settings, rng) (bindings/common.hh:677-683 ->
+        planning/simplify.hh:192-260) on the CPU rake.  rng is accepted for the reference's signature; the
+        supported operations (SHORTCUT, BSPLINE) draw nothing from it.  The result carries `status`
+        (0 done, 1 stopped at settings.max_path_len) and `validated_edges` (validate_motion calls made)."""
+        dim = self.dimension()
+        p = np.ascontiguousarray(path, np.float32).reshape(-1, dim)
+        settings = settings or SimplifySettings()
+        cs = settings.c()
+        res = _lib.VgpuPlanResult()
+        st = C.c_int32(0)
+        cap = max(4 * p.shape[0], 64)
+        while True:
+            out = np.empty((cap, dim), np.float32)
+            rc = load().vgpu_cpu_simplify(C.byref(self.c_robot), environment.host_handle(),
+                                          p.ctypes.data_as(_lib.F32P), p.shape[0], C.byref(cs),
+                                          out.ctypes.data_as(_lib.F32P), cap, C.byref(res), C.byref(st))
+            if rc == _lib.VGPU_ERR_UNSUPPORTED and settings.unsupported():
+                raise VgpuError(f"vamp_gpu: unsupported: simplify: {settings.unsupported()}")
+            if rc == _lib.VGPU_OK or res.path_len <= cap:
+                check(rc)
+                break
+            cap = int(res.path_len)
+        r = PlanningResult(out[:res.path_len].copy(), float(res.cost), int(res.iterations), [], int(res.nanoseconds),
+                           True)
+        r.status, r.validated_edges = int(st.value), int(res.size[0])
+        return r
+
+    def simplify_capacity(self, max_len: int, settings: SimplifySettings, n_paths: int = 1) -> int:
+        """Waypoint slots per path that no simplify run can outgrow: every B-spline step at most doubles the
+        segments, (max_len - 1) * 2^(max_iterations * bspline.max_steps) + 1, clamped so that n_paths * capacity
+        stays below the batch call's 2^31 limit."""
+        steps = int(settings.max_iterations) * int(settings.bspline.max_steps) * sum(
+            int(o) == SimplifyRoutine.BSPLINE for o in settings.operations)
+        worst = (max(int(max_len), 2) - 1) * 2 ** min(steps, 40) + 1
+        return int(max(min(worst, (2 ** 31 - 1) // max(int(n_paths), 1)), 1))
+
+    def simplify_batch(self, paths, environment: Environment, settings: Optional[SimplifySettings] = None,
+                       ctx: Optional[Context] = None, capacity: Optional[int] = None):
+        """simplify() of every path of a list in one environment, in lockstep on the GPU
+        (vgpu_simplify_paths_host): returns ([PlanningResult], status uint8[n]); each result equals
+        simplify()'s bit for bit (with settings.max_path_len = capacity where a path stops with status 1).
+        capacity: waypoint slots per path, default simplify_capacity() of the longest path."""
+        ctx = ctx or context()
+        dim = self.dimension()
+        settings = settings or SimplifySettings()
+        ps = [np.ascontiguousarray(p, np.float32).reshape(-1, dim) for p in paths]
+        n = len(ps)
+        if n == 0:
+            return [], np.zeros(0, np.uint8)
+        longest = max(p.shape[0] for p in ps)
+        cap = int(capacity) if capacity is not None else self.simplify_capacity(longest, settings, n)
+        if cap < longest:
+            raise ValueError(f"capacity {cap} below the longest path ({longest} waypoints)")
+        w = np.zeros((n, cap, dim), np.float32)
+        ln = np.empty(n, np.uint32)
+        for i, p in enumerate(ps):
+            w[i, :p.shape[0]] = p
+            ln[i] = p.shape[0]
+        it = np.empty(n, np.uint32)
+        st = np.empty(n, np.uint8)
+        cost = np.empty(n, np.float32)
+        cs = settings.c()
+        check(load().vgpu_simplify_paths_host(ctx.h, C.byref(self.c_robot), environment.handle(ctx),
+                                              w.ctypes.data_as(_lib.F32P), cap, ln.ctypes.data_as(_lib.U32P), n,
+                                              C.byref(cs), it.ctypes.data_as(_lib.U32P), st.ctypes.data_as(_lib.U8P),
+                                              cost.ctypes.data_as(_lib.F32P)), ctx.h)
+        out = []
+        for i in range(n):
+            r = PlanningResult(w[i, :ln[i]].copy(), float(cost[i]), int(it[i]), [], 0, True)
+            r.status = int(st[i])
+            out.append(r)
+        return out, st
+
+    def simplify_stats(self, ctx: Optional[Context] = None) -> dict:
+        """counters of the context's last simplify_batch / simplify_device call"""
+        ctx = ctx or context()
+        s = (C.c_uint64 * 3)()
+        check(load().vgpu_simplify_stats(ctx.h, s), ctx.h)
+        return {"rounds": int(s[0]), "validate_calls": int(s[1]), "edges": int(s[2])}
+
     def roadmap(self, start, goal, environment: Environment, settings: Optional[PRMSettings] = None,
                 rng: Optional[Halton] = None, ctx: Optional[Context] = None):
         """vamp.<robot>.roadmap(start, goal, environment, settings, rng) (bindings/common.hh:312-321,667 ->
@@ -954,6 +1087,18 @@ class Robot:
                                                 C.c_void_p(nblocks_ptr or 0), C.c_void_p(block_ok_ptr), block_cap,
                                                 C.byref(total)), ctx.h)
         return int(total.value)
+
+    def simplify_device(self, waypoints_ptr: int, capacity: int, len_ptr: int, n_paths: int, environment: Environment,
+                        settings: Optional[SimplifySettings] = None, iterations_ptr: int = 0, status_ptr: int = 0,
+                        cost_ptr: int = 0, ctx: Optional[Context] = None):
+        """vgpu_simplify_paths over device memory: waypoints float32 [n_paths][capacity][dim] and len uint32
+        [n_paths] in place; iterations uint32, status uint8 and cost float32 [n_paths] are optional."""
+        ctx = ctx or context()
+        cs = (settings or SimplifySettings()).c()
+        check(load().vgpu_simplify_paths(ctx.h, C.byref(self.c_robot), environment.handle(ctx),
+                                         C.c_void_p(waypoints_ptr), int(capacity), C.c_void_p(len_ptr), int(n_paths),
+                                         C.byref(cs), C.c_void_p(iterations_ptr or 0), C.c_void_p(status_ptr or 0),
+                                         C.c_void_p(cost_ptr or 0)), ctx.h)
 
     def validate_device(self, starts_ptr: int, goals_ptr: int, n: int, environment: Environment, ok_ptr: int,
                         nblocks_ptr: int = 0, ctx: Optional[Context] = None):

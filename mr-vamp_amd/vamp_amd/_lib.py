@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VAMP_AMD_LIB") or os.path.join(HERE, "libvampgpu.so")
 
 VGPU_OK = 0
+VGPU_ERR_UNSUPPORTED = -4
 VGPU_ROBOT_PANDA = 1
 VGPU_ROBOT_FETCH = 2
 VGPU_ROBOT_PANDA_PAIR = 3
@@ -42,6 +43,12 @@ class VgpuRrtcSettings(C.Structure):
 class VgpuPlanResult(C.Structure):
     _fields_ = [("solved", C.c_int32), ("iterations", C.c_uint64), ("nanoseconds", C.c_int64),
                 ("size", C.c_uint64 * 2), ("cost", C.c_float), ("path_len", C.c_size_t)]
+
+
+class VgpuSimplifySettings(C.Structure):
+    _fields_ = [("max_iterations", C.c_uint64), ("interpolate", C.c_uint64), ("n_operations", C.c_int32),
+                ("operations", C.c_int32 * 8), ("bspline_max_steps", C.c_uint64), ("bspline_min_change", C.c_float),
+                ("bspline_midpoint_interpolation", C.c_float), ("max_path_len", C.c_uint64)]
 
 
 # every exported symbol of include/vamp_gpu.h with its signature (restype, argtypes)
@@ -157,6 +164,14 @@ SIGNATURES = {
     "vgpu_cpu_validate_vector": (C.c_int, [C.POINTER(VgpuRobot), VP, F32P, F32P, C.c_float, C.POINTER(C.c_int)]),
     "vgpu_cpu_rrtc": (C.c_int, [C.POINTER(VgpuRobot), VP, F32P, F32P, C.c_size_t, C.POINTER(VgpuRrtcSettings),
                                 C.POINTER(C.c_uint64), F32P, C.c_size_t, C.POINTER(VgpuPlanResult)]),
+    "vgpu_simplify_settings_default": (C.c_int, [C.POINTER(VgpuSimplifySettings)]),
+    "vgpu_cpu_simplify": (C.c_int, [C.POINTER(VgpuRobot), VP, F32P, C.c_size_t, C.POINTER(VgpuSimplifySettings), F32P,
+                                    C.c_size_t, C.POINTER(VgpuPlanResult), I32P]),
+    "vgpu_simplify_paths": (C.c_int, [VP, C.POINTER(VgpuRobot), VP, VP, C.c_size_t, VP, C.c_size_t,
+                                      C.POINTER(VgpuSimplifySettings), VP, VP, VP]),
+    "vgpu_simplify_paths_host": (C.c_int, [VP, C.POINTER(VgpuRobot), VP, F32P, C.c_size_t, U32P, C.c_size_t,
+                                           C.POINTER(VgpuSimplifySettings), U32P, U8P, F32P]),
+    "vgpu_simplify_stats": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
     "vgpu_build_roadmap_host": (C.c_int, [VP, C.POINTER(VgpuRobot), VP, F32P, C.c_size_t, C.c_double, C.c_double,
                                           C.POINTER(C.c_size_t), U32P, C.c_size_t, C.POINTER(C.c_size_t), U32P]),
 }
