@@ -274,6 +274,55 @@ int vgpu_build_roadmap_host(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *en
                             double space_measure, double gamma_scale, size_t *offsets, uint32_t *adj,
                             size_t adj_cap, size_t *n_adj, uint32_t *component);
 
+/* ---- roadmap queries: PRM::solve's search half (planning/prm.hh:168-187, planning/utils.hh:75-142) ------ */
+/* All pointers below are device memory on ctx unless a function says "host".  A graph is CSR: offsets[n+1]
+ * (uint64, as vgpu_roadmap_assemble_device writes it), adj[offsets[n]]; slot e of vertex i is the directed
+ * edge i -> adj[e].  n < 2^31, offsets[n] < 2^32, S * n < 2^32.  Every call is synchronous (one host read per
+ * round) and every loop is bounded (rounds <= n + 1): exceeding a bound returns VGPU_ERR_INTERNAL. */
+/* w[e] = Space<dim>::distance(V[i], V[adj[e]]) for every slot e of vertex i (nn.hh:53-57), computed by the
+ * neighbour query's own device function: equal bit for bit to the dist vgpu_roadmap_knn returned for the
+ * pair, the same for both directions.  dim in {6, 7, 8, 14}; n_adj must equal offsets[n]. */
+int vgpu_roadmap_edge_weights(vgpu_ctx *ctx, int dim, const float *V, size_t n, const uint64_t *offsets,
+                              const uint32_t *adj, size_t n_adj, float *w);
+/* S single-source searches over one graph in lockstep (mr-vamp_amd/csrc/vgpu_roadmap_query.hip).  Search s
+ * starts at sources[s] and sees only vertices with index <= limits[s] (limits NULL: all) -- the roadmap as it
+ * stood when vertex limits[s] was added; a source above its limit or >= n is VGPU_ERR_INVALID_ARG.
+ * Weights are >= 0 or +inf (a +inf slot is ignored); a negative or NaN weight, a slot index >= n and
+ * non-monotone offsets are VGPU_ERR_INVALID_ARG.  Outputs [S][n]:
+ *   g       the least fixed point of g[src] = 0, g[v] = min_u fl32(g[u] + w(u, v)) -- what a Dijkstra in
+ *           float arithmetic computes; +inf where unreachable (or where every sum overflows);
+ *   hops    BFS depth from the source over TIGHT edges, those with bits(fl32(g[u] + w(u, v))) == bits(g[v])
+ *           and g[v] finite;
+ *   parent  the smallest u with a tight edge into v and hops[u] == hops[v] - 1; parent[src] = src.
+ * Unreachable vertices get UINT32_MAX in hops and parent.  The result does not depend on execution order;
+ * among equal-cost paths the parent chain is one with the fewest waypoints.  hops and parent may both be
+ * NULL (g only). */
+int vgpu_roadmap_sssp(vgpu_ctx *ctx, size_t n, const uint64_t *offsets, const uint32_t *adj, const float *w,
+                      const uint32_t *sources, const uint32_t *limits, size_t S, float *g, uint32_t *hops,
+                      uint32_t *parent);
+/* counters of the context's last vgpu_roadmap_sssp or vgpu_roadmap_bottleneck call: out[0] relaxation rounds,
+ * out[1] slots relaxed in them (a frontier item relaxes every slot of its vertex), out[2] frontier items
+ * processed, out[3] host reads (one per relaxation round and per level of the tight-edge BFS, plus three) */
+int vgpu_roadmap_sssp_stats(const vgpu_ctx *ctx, uint64_t out[4]);
+/* b[s][v] = the minimum over paths from sources[s] to v of the largest vertex index on the path (endpoints
+ * included); UINT32_MAX where unreachable.  The same frontier engine over (max, min) on uint32.  With
+ * sources = {0}, b[0][1] is the vertex at whose insertion PRM::solve's union-find first joins start and goal. */
+int vgpu_roadmap_bottleneck(vgpu_ctx *ctx, size_t n, const uint64_t *offsets, const uint32_t *adj,
+                            const uint32_t *sources, size_t S, uint32_t *b);
+/* The path of search s from its source to targets[s] by walking parent[s][.]: idx[s][0 .. len[s]-1], source
+ * first, idx[S][cap].  len[s] = 0: the target is unreachable (or >= n); len[s] = UINT32_MAX: the path has
+ * more than cap vertices or the walk did not end within n steps (nothing is written past cap). */
+int vgpu_roadmap_extract_paths(vgpu_ctx *ctx, const uint32_t *parent, size_t n, const uint32_t *targets, size_t S,
+                               size_t cap, uint32_t *idx, uint32_t *len);
+/* The same results on the host CPU, host pointers, no context (mr-vamp_amd/csrc/cpu/vcpu_roadmap_query.cpp):
+ * a binary-heap Dijkstra per search, then the tight-edge BFS and the parent rule; a union-find over the
+ * vertices in index order for the bottleneck.  hops and parent may both be NULL. */
+int vgpu_cpu_roadmap_sssp(size_t n, const uint64_t *offsets, const uint32_t *adj, const float *w,
+                          const uint32_t *sources, const uint32_t *limits, size_t S, float *g, uint32_t *hops,
+                          uint32_t *parent);
+int vgpu_cpu_roadmap_bottleneck(size_t n, const uint64_t *offsets, const uint32_t *adj, const uint32_t *sources,
+                                size_t S, uint32_t *b);
+
 /* ---- CPU rake (host AVX2; no context, no GPU) --------------------------------------------------- */
 /* The reference's single-call entry points stay on the CPU (a GPU launch costs far more than one
  * ~2 us edge): the same generated op sequence as the kernels over one 8-lane AVX2 register per

@@ -26,6 +26,7 @@
 #include "vgpu_host_env.hh"
 #include "vgpu_lean.hh"
 #include "vgpu_ops.hh"
+#include "vgpu_roadmap_query.hh"
 #include "vgpu_simplify.hh"
 #include "gen/radii.inc"
 
@@ -294,6 +295,8 @@ struct vgpu_ctx {
     size_t simp_bytes = 0;
     uint32_t* simp_host = nullptr;
     uint64_t simp_stats[3] = {0, 0, 0};
+    // roadmap queries (vgpu_roadmap_query.hip): frontier workspace, the pinned round total, the last call's counters
+    vgpu::QueryState rq;
     // optional phase timing
     bool prof = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -456,6 +459,7 @@ extern "C" void vgpu_ctx_destroy(vgpu_ctx* c)
     if (c->dbg) (void)hipFree(c->dbg);
     if (c->simp) (void)hipFree(c->simp);
     if (c->simp_host) (void)hipHostFree(c->simp_host);
+    vgpu::query_free(c->rq);
     if (c->tick) (void)hipFree(c->tick);
     if (c->total_host) (void)hipHostFree(c->total_host);
     for (auto& ev : c->ev)
@@ -2639,4 +2643,104 @@ try {
     if (cost) HIPCHK(c, hipMemcpyAsync(cost, cd, n_paths * 4, hipMemcpyDeviceToHost, c->cur));
     HIPCHK(c, hipStreamSynchronize(c->cur));
     return VGPU_OK;
+} VGPU_ABI_CATCH
+
+// ---- roadmap queries (planning/prm.hh:168-187; kernels and round loops in vgpu_roadmap_query.hip) --------------
+extern "C" hipError_t vgpu_launch_edge_weights(int dim, const float* V, uint32_t n, const unsigned long long* off,
+                                               const uint32_t* adj, unsigned long long n_adj, float* w, uint32_t* bad,
+                                               hipStream_t st);
+
+static int query_done(vgpu_ctx* c, const vgpu::QueryStatus& s)
+{
+    if (s.code == VGPU_OK) return VGPU_OK;
+    c->err = s.code == VGPU_ERR_HIP ? std::string(s.msg) + ": " + hipGetErrorString(s.hip) : std::string(s.msg);
+    return s.code;
+}
+
+// n < 2^31 and S * n < 2^32: an item (search, vertex) is one 32-bit word
+static int query_sizes(vgpu_ctx* c, size_t n, size_t S)
+{
+    if (n >= ((size_t)1 << 31)) return fail(c, VGPU_ERR_INVALID_ARG, "too many vertices");
+    if (S >= ((size_t)1 << 32) || (n && S > (((size_t)1 << 32) - 1) / n))
+        return fail(c, VGPU_ERR_INVALID_ARG, "S * n must be below 2^32 (split the batch)");
+    return VGPU_OK;
+}
+
+extern "C" int vgpu_roadmap_edge_weights(vgpu_ctx* c, int dim, const float* V, size_t n, const uint64_t* offsets,
+                                         const uint32_t* adj, size_t n_adj, float* w)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    if (dim != 6 && dim != 7 && dim != 8 && dim != 14) return fail(c, VGPU_ERR_INVALID_ARG, "dim must be 6, 7, 8 or 14");
+    if (n >= ((size_t)1 << 31) || n_adj >= ((size_t)1 << 32)) return fail(c, VGPU_ERR_INVALID_ARG, "graph too large");
+    if (n == 0) return n_adj ? fail(c, VGPU_ERR_INVALID_ARG, "slots without vertices") : VGPU_OK;
+    if (!V || !offsets || (n_adj && (!adj || !w))) return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    char* d;
+    int rc = stage(c, 256, &d);
+    if (rc) return rc;
+    uint64_t ends[2] = {0, 0};  // offsets[0] is read with offsets[n]: one read-back
+    HIPCHK(c, hipMemsetAsync(d, 0, 4, c->cur));
+    HIPCHK(c, hipMemcpyAsync(&ends[0], offsets, 8, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipMemcpyAsync(&ends[1], offsets + n, 8, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipStreamSynchronize(c->cur));
+    if (ends[0] != 0 || ends[1] != n_adj) return fail(c, VGPU_ERR_INVALID_ARG, "offsets[0] != 0 or offsets[n] != n_adj");
+    HIPCHK(c, vgpu_launch_edge_weights(dim, V, (uint32_t)n, (const unsigned long long*)offsets, adj, n_adj, w,
+                                       (uint32_t*)d, c->cur));
+    uint32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d, 4, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipStreamSynchronize(c->cur));
+    if (bad) return fail(c, VGPU_ERR_INVALID_ARG, "graph: offsets not monotone or a slot index >= n");
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_roadmap_sssp(vgpu_ctx* c, size_t n, const uint64_t* offsets, const uint32_t* adj, const float* w,
+                                 const uint32_t* sources, const uint32_t* limits, size_t S, float* g, uint32_t* hops,
+                                 uint32_t* parent)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    for (auto& x : c->rq.stats) x = 0;
+    if ((hops == nullptr) != (parent == nullptr)) return fail(c, VGPU_ERR_INVALID_ARG, "hops and parent: both or neither");
+    int rc = query_sizes(c, n, S);
+    if (rc) return rc;
+    if (S == 0) return VGPU_OK;
+    if (n == 0) return fail(c, VGPU_ERR_INVALID_ARG, "a source >= n or above its limit");
+    if (!offsets || !sources || !g) return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    HIPCHK(c, ctx_device(c));
+    return query_done(c, vgpu::query_sssp(c->rq, (uint32_t)n, (const unsigned long long*)offsets, adj, w, sources,
+                                          limits, (uint32_t)S, g, hops, parent, c->cur));
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_roadmap_sssp_stats(const vgpu_ctx* c, uint64_t out[4])
+try {
+    if (!c || !out) return VGPU_ERR_INVALID_ARG;
+    for (int k = 0; k < 4; ++k) out[k] = c->rq.stats[k];
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_roadmap_bottleneck(vgpu_ctx* c, size_t n, const uint64_t* offsets, const uint32_t* adj,
+                                       const uint32_t* sources, size_t S, uint32_t* b)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    for (auto& x : c->rq.stats) x = 0;
+    int rc = query_sizes(c, n, S);
+    if (rc) return rc;
+    if (S == 0) return VGPU_OK;
+    if (n == 0) return fail(c, VGPU_ERR_INVALID_ARG, "a source >= n");
+    if (!offsets || !sources || !b) return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    HIPCHK(c, ctx_device(c));
+    return query_done(c, vgpu::query_bottleneck(c->rq, (uint32_t)n, (const unsigned long long*)offsets, adj, sources,
+                                                (uint32_t)S, b, c->cur));
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_roadmap_extract_paths(vgpu_ctx* c, const uint32_t* parent, size_t n, const uint32_t* targets,
+                                          size_t S, size_t cap, uint32_t* idx, uint32_t* len)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    int rc = query_sizes(c, n, S);
+    if (rc) return rc;
+    if (S == 0) return VGPU_OK;
+    if (cap >= ((size_t)1 << 32)) return fail(c, VGPU_ERR_INVALID_ARG, "cap must be below 2^32");
+    if (!targets || !len || (n && !parent) || (cap && !idx)) return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    HIPCHK(c, ctx_device(c));
+    return query_done(c, vgpu::query_extract(parent, (uint32_t)n, targets, (uint32_t)S, (uint32_t)cap, idx, len,
+                                             c->cur));
 } VGPU_ABI_CATCH

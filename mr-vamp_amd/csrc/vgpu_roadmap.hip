@@ -269,6 +269,42 @@ __global__ __launch_bounds__(256) void edge_pairs_kernel(uint32_t q_first, uint3
     pairs[(size_t)off[i] + m] = v | (j << 32);
 }
 
+// w[e] = Space<D>::distance(V[adj[e]], V[i]) for every CSR slot e of vertex i: config_sumsq and the correctly
+// rounded sqrt exactly as knn_kernel applies them to (candidate, query), so a weight has the bits of the
+// query's dist; a - b and b - a square alike, so both directions of an edge agree.  One wave per vertex, lanes
+// striding its slots.  *bad = 1 (and nothing read past the arrays) on offsets that are not monotone within
+// n_adj or a slot index >= n.
+template <int D>
+__global__ __launch_bounds__(256) void edge_weights_kernel(const float* __restrict__ V, uint32_t n,
+                                                           const unsigned long long* __restrict__ off,
+                                                           const uint32_t* __restrict__ adj, unsigned long long n_adj,
+                                                           float* __restrict__ w, uint32_t* __restrict__ bad)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6, waves = (gridDim.x * 256u) >> 6;
+    for (uint32_t i = wave; i < n; i += waves) {
+        const unsigned long long lo = off[i], hi = off[i + 1];
+        if (lo > hi || hi > n_adj) {
+            *bad = 1u;
+            continue;
+        }
+        float me[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) me[j] = V[(size_t)i * D + j];
+        for (unsigned long long e = lo + lane; e < hi; e += 64) {
+            const uint32_t t = adj[e];
+            if (t >= n) {
+                *bad = 1u;
+                continue;
+            }
+            float other[D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) other[j] = V[(size_t)t * D + j];
+            w[e] = __builtin_sqrtf(config_sumsq<D>(other, me));
+        }
+    }
+}
+
 }  // namespace vgpu
 
 template <int D, int K>
@@ -333,6 +369,23 @@ hipError_t vgpu_launch_edge_gather(const float* V, uint32_t q_first, uint32_t q_
     if (threads == 0) return hipSuccess;
     hipLaunchKernelGGL(vgpu::edge_gather_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, V, q_first,
                        q_count, dim, nbr, kmax, cnt, off, starts, goals);
+    return hipGetLastError();
+}
+
+// dim in {6, 7, 8, 14} is checked by the caller; bad: one zeroed device word
+hipError_t vgpu_launch_edge_weights(int dim, const float* V, uint32_t n, const unsigned long long* off,
+                                    const uint32_t* adj, unsigned long long n_adj, float* w, uint32_t* bad,
+                                    hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    const dim3 grid(std::min<uint32_t>(4096u, (n + 3u) / 4u)), block(256);
+    switch (dim) {
+    case 6: hipLaunchKernelGGL(vgpu::edge_weights_kernel<6>, grid, block, 0, st, V, n, off, adj, n_adj, w, bad); break;
+    case 7: hipLaunchKernelGGL(vgpu::edge_weights_kernel<7>, grid, block, 0, st, V, n, off, adj, n_adj, w, bad); break;
+    case 8: hipLaunchKernelGGL(vgpu::edge_weights_kernel<8>, grid, block, 0, st, V, n, off, adj, n_adj, w, bad); break;
+    case 14: hipLaunchKernelGGL(vgpu::edge_weights_kernel<14>, grid, block, 0, st, V, n, off, adj, n_adj, w, bad); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -934,6 +934,55 @@ class Robot:
         rm.iterations = taken + 1
         return rm
 
+    def prm(self, start, goal, environment: Environment, settings: Optional[PRMSettings] = None,
+            rng: Optional[Halton] = None, ctx: Optional[Context] = None, _first_chunk: int = 1024) -> PlanningResult:
+        """vamp.<robot>.prm(start, goal, environment, settings, rng) (bindings/common.hh:296-310 -> PRM::solve,
+        planning/prm.hh:43-196) on the GPU roadmap.  A valid straight line answers at once (path [start, goal],
+        iterations 0, size [1, 1], rng untouched).  Otherwise the roadmap is built over a growing number of
+        draws (_first_chunk, then x4, clipped by max_iterations and max_samples); the build is causal, so every
+        stage's graph is a prefix of the next and the result does not depend on the schedule.  The first stage
+        in which start and goal connect gives n* = Roadmap.connect_index(), the vertex at whose insertion the
+        reference's union-find joins them; the path is the shortest one over vertices 0 .. n*
+        (Roadmap.shortest_paths with limit n*), cost = g[goal], iterations = the draws up to and including
+        n*'s, size = [n* + 1, 0], and rng advances by exactly those draws.  Unsolved: empty path, iterations =
+        draws taken + 1, size = [vertices, 0].  One goal only: the roadmap fixes start at index 0 and goal at 1."""
+        import time
+
+        from . import roadmap as _rm
+        dim = self.dimension()
+        g = np.ascontiguousarray(goal, np.float32)
+        if g.size != dim:
+            raise VgpuError("vamp_gpu: unsupported: prm: a list of goals is not supported (one goal configuration)")
+        g = g.reshape(dim)
+        s = np.ascontiguousarray(start, np.float32).reshape(dim)
+        settings = settings or PRMSettings(PRMNeighborParams(dim, self.space_measure()))
+        rng = rng or self.halton()
+        t0 = time.perf_counter_ns()
+        if self.validate_motion(s, g, environment):
+            # cost stays 0 as in the reference, which sets it only on the searched branch (plan.hh:175)
+            return PlanningResult(np.stack([s, g]), 0.0, 0, [1, 1], time.perf_counter_ns() - t0, True)
+        max_it, max_s = int(settings.max_iterations), int(settings.max_samples)
+        n_draws = min(max(int(_first_chunk), 1), max_it)
+        while True:
+            rows, draws = _rm.roadmap_vertices(self, environment, n_draws, rng.index, s, g, max(max_s, 2), ctx)
+            draws = draws.cpu().numpy()
+            full = max_s <= 2 or len(draws) >= max_s  # the sample limit ends the reference's loop here
+            rm = _rm.build_roadmap_edges(self, environment, rows.cpu().numpy(), settings.neighbor_params.gamma_scale,
+                                         settings.neighbor_params.space_measure, ctx)
+            at = rm.connect_index(0, 1, ctx) if max_s > 2 else None
+            if at is not None:
+                path, cost, _ = rm.shortest_paths([0], [1], at, ctx)[0]
+                taken = int(draws[at]) - rng.index + 1
+                rng.skip(taken)
+                return PlanningResult(rm.vertices[path.astype(np.int64)].copy(), float(cost), taken, [at + 1, 0],
+                                      time.perf_counter_ns() - t0, True)
+            if full or n_draws >= max_it:
+                taken = 0 if max_s <= 2 else (int(draws[max_s - 1]) - rng.index + 1 if full else max_it)
+                rng.skip(taken)
+                return PlanningResult(np.zeros((0, dim), np.float32), 0.0, taken + 1, [len(rm.vertices), 0],
+                                      time.perf_counter_ns() - t0, False)
+            n_draws = min(4 * n_draws, max_it)
+
     def cpu_validate_vector(self, start, vector, distance: float, environment: Environment) -> bool:
         """planning::validate_vector<Robot, 8, resolution>(start, vector, distance, env)."""
         s = np.ascontiguousarray(start, np.float32).reshape(self.dimension())

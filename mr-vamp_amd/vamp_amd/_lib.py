@@ -26,6 +26,7 @@ F32P = C.POINTER(C.c_float)
 U8P = C.POINTER(C.c_uint8)
 I32P = C.POINTER(C.c_int32)
 U32P = C.POINTER(C.c_uint32)
+U64P = C.POINTER(C.c_uint64)
 VP = C.c_void_p
 
 
@@ -174,6 +175,13 @@ SIGNATURES = {
     "vgpu_simplify_stats": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
     "vgpu_build_roadmap_host": (C.c_int, [VP, C.POINTER(VgpuRobot), VP, F32P, C.c_size_t, C.c_double, C.c_double,
                                           C.POINTER(C.c_size_t), U32P, C.c_size_t, C.POINTER(C.c_size_t), U32P]),
+    "vgpu_roadmap_edge_weights": (C.c_int, [VP, C.c_int, VP, C.c_size_t, VP, VP, C.c_size_t, VP]),
+    "vgpu_roadmap_sssp": (C.c_int, [VP, C.c_size_t, VP, VP, VP, VP, VP, C.c_size_t, VP, VP, VP]),
+    "vgpu_roadmap_sssp_stats": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
+    "vgpu_roadmap_bottleneck": (C.c_int, [VP, C.c_size_t, VP, VP, VP, C.c_size_t, VP]),
+    "vgpu_roadmap_extract_paths": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t, C.c_size_t, VP, VP]),
+    "vgpu_cpu_roadmap_sssp": (C.c_int, [C.c_size_t, U64P, U32P, F32P, U32P, U32P, C.c_size_t, F32P, U32P, U32P]),
+    "vgpu_cpu_roadmap_bottleneck": (C.c_int, [C.c_size_t, U64P, U32P, U32P, C.c_size_t, U32P]),
 }
 
 _lib = None

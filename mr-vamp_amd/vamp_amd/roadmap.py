@@ -186,6 +186,229 @@ class Roadmap:
     def n_edges(self) -> int:
         return int(self.offsets[-1]) // 2
 
+    # ---- queries (PRM::solve's search half, prm.hh:168-187): vgpu_roadmap_query.hip -------------------------
+    def _device(self, ctx=None):
+        """(ctx, DeviceGraph) of this roadmap: vertices, CSR arrays and edge weights uploaded / computed once"""
+        from . import context
+        ctx = ctx or context()
+        if getattr(self, "_graph", None) is None or self._graph.ctx is not ctx:
+            import torch
+            self._graph = DeviceGraph(torch, self.offsets, self.adj, ctx, self.vertices)
+        return ctx, self._graph
+
+    @property
+    def weights(self) -> np.ndarray:
+        """float32 [len(adj)]: slot e of vertex i weighs Space<dim>::distance(V[i], V[adj[e]]), the distance the
+        neighbour query measured for the pair (vgpu_roadmap_edge_weights); computed once and kept."""
+        if getattr(self, "_weights", None) is None:
+            g = self._device()[1]
+            self._weights = g.w.cpu().numpy()[:g.n_adj]
+        return self._weights
+
+    def shortest_paths(self, sources, targets, limit=None, ctx=None):
+        """One search per (source, target) pair, batched on the GPU (vgpu_roadmap_sssp +
+        vgpu_roadmap_extract_paths).  limit (None, one index, or one per pair): the search sees only vertices
+        with index <= limit, the roadmap as it stood when that vertex was added.  Returns per pair
+        (path: vertex indices source first, empty if unreachable; cost = g[target] as np.float32, inf if
+        unreachable; hops = len(path) - 1, or -1)."""
+        import torch
+        ctx, g = self._device(ctx)
+        src = np.atleast_1d(np.asarray(sources, np.int64)).astype(np.uint32)
+        tgt = np.atleast_1d(np.asarray(targets, np.int64)).astype(np.uint32)
+        if src.shape != tgt.shape or src.ndim != 1:
+            raise ValueError("shortest_paths: one target per source")
+        S, n = len(src), g.n
+        if S == 0:
+            return []
+        if len(tgt) and int(tgt.max()) >= n:
+            raise ValueError("shortest_paths: target index out of range")
+        lim = None if limit is None else np.broadcast_to(np.asarray(limit, np.int64), (S,)).astype(np.uint32)
+        gg, hops, parent = sssp_device(torch, g, src, lim, ctx)
+        idx, ln = extract_paths_device(torch, parent, tgt, n, ctx)
+        cost = gg[torch.arange(S, device=gg.device), torch.from_numpy(tgt.astype(np.int64)).to(gg.device)].cpu().numpy()
+        idx, ln = idx.cpu().numpy().view(np.uint32), ln.cpu().numpy().view(np.uint32)
+        out = []
+        for s in range(S):
+            if ln[s] == 0xffffffff:
+                raise RuntimeError("shortest_paths: a parent walk did not end within n steps")
+            path = idx[s, :ln[s]].copy()
+            out.append((path, np.float32(cost[s]), int(ln[s]) - 1))
+        return out
+
+    def connect_index(self, source: int = 0, target: int = 1, ctx=None):
+        """The vertex at whose insertion source and target first share a connected component -- the smallest
+        possible largest vertex index of a path between them (vgpu_roadmap_bottleneck); None if they never do.
+        With the defaults: the vertex at which PRM::solve stops (prm.hh:168-175)."""
+        import torch
+        ctx, g = self._device(ctx)
+        if not 0 <= int(target) < g.n:
+            raise ValueError("connect_index: target index out of range")
+        b = bottleneck_device(torch, g, np.array([source], np.uint32), ctx)
+        v = int(b[0, int(target)].item()) & 0xffffffff
+        return None if v == 0xffffffff else v
+
+    def sssp_stats(self, ctx=None) -> dict:
+        """counters of the context's last shortest_paths / connect_index call"""
+        from . import context
+        return sssp_stats(ctx or context())
+
+
+class DeviceGraph:
+    """A CSR graph in device memory for the query kernels: offsets int64 [n+1] (the uint64 the C ABI reads),
+    adj int32 [n_adj] (uint32 bits) and weights float32 [n_adj] -- given, or computed from the vertices
+    [n, dim] by vgpu_roadmap_edge_weights."""
+
+    def __init__(self, torch, offsets, adj, ctx, vertices=None, weights=None):
+        from ._lib import check, load
+        self.ctx = ctx
+        dev = torch.device("cuda", torch.cuda.current_device())
+        ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        off = np.ascontiguousarray(offsets).astype(np.int64)
+        self.n = len(off) - 1
+        self.n_adj = int(off[-1]) if self.n >= 0 and len(off) else 0
+        a = np.ascontiguousarray(adj, np.uint32)[:self.n_adj]
+        self.dev = dev
+        self.offsets = torch.from_numpy(off).to(dev)
+        self.adj = torch.from_numpy(np.concatenate([a, np.zeros(1, np.uint32)]).view(np.int32)).to(dev)
+        if weights is not None:
+            wv = np.ascontiguousarray(weights, np.float32)[:self.n_adj]
+            self.w = torch.from_numpy(np.concatenate([wv, np.zeros(1, np.float32)])).to(dev)
+            return
+        self.w = torch.zeros(self.n_adj + 1, dtype=torch.float32, device=dev)
+        V = torch.from_numpy(np.ascontiguousarray(vertices, np.float32)).to(dev)
+        dim = V.shape[1] if V.ndim == 2 else 0
+        check(load().vgpu_roadmap_edge_weights(ctx.h, dim, V.data_ptr(), self.n, self.offsets.data_ptr(),
+                                               self.adj.data_ptr(), self.n_adj, self.w.data_ptr()), ctx.h)
+
+
+def _u32_tensor(torch, a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32).copy()).to(dev)
+
+
+def sssp_device(torch, graph: DeviceGraph, sources, limits=None, ctx=None, parents: bool = True):
+    """vgpu_roadmap_sssp: one search per source (and prefix limit) over a DeviceGraph.  Returns device tensors
+    (g float32 [S, n], hops int32 [S, n], parent int32 [S, n]); hops and parent hold uint32 bits (-1 =
+    UINT32_MAX = unreachable) and are None with parents=False."""
+    from ._lib import check, load
+    ctx = ctx or graph.ctx
+    src = np.ascontiguousarray(sources, np.uint32).ravel()
+    S, n, dev = len(src), graph.n, graph.dev
+    ts = _u32_tensor(torch, src if S else np.zeros(1, np.uint32), dev)
+    tl = None if limits is None else _u32_tensor(torch, np.ascontiguousarray(limits, np.uint32).ravel(), dev)
+    if tl is not None and tl.numel() != S:
+        raise ValueError("sssp_device: one limit per source")
+    g = torch.empty((S, n), dtype=torch.float32, device=dev)
+    hops = torch.empty((S, n), dtype=torch.int32, device=dev) if parents else None
+    parent = torch.empty((S, n), dtype=torch.int32, device=dev) if parents else None
+    check(load().vgpu_roadmap_sssp(ctx.h, n, graph.offsets.data_ptr(), graph.adj.data_ptr(), graph.w.data_ptr(),
+                                   ts.data_ptr(), tl.data_ptr() if tl is not None and S else None, S, g.data_ptr(),
+                                   hops.data_ptr() if parents else None, parent.data_ptr() if parents else None), ctx.h)
+    return g, hops, parent
+
+
+def bottleneck_device(torch, graph: DeviceGraph, sources, ctx=None):
+    """vgpu_roadmap_bottleneck: b int32 [S, n] (uint32 bits, -1 = unreachable), a device tensor."""
+    from ._lib import check, load
+    ctx = ctx or graph.ctx
+    src = np.ascontiguousarray(sources, np.uint32).ravel()
+    S, n, dev = len(src), graph.n, graph.dev
+    ts = _u32_tensor(torch, src if S else np.zeros(1, np.uint32), dev)
+    b = torch.empty((S, n), dtype=torch.int32, device=dev)
+    check(load().vgpu_roadmap_bottleneck(ctx.h, n, graph.offsets.data_ptr(), graph.adj.data_ptr(), ts.data_ptr(), S,
+                                         b.data_ptr()), ctx.h)
+    return b
+
+
+def extract_paths_device(torch, parent, targets, cap: int, ctx):
+    """vgpu_roadmap_extract_paths over sssp_device's parent [S, n]: (idx int32 [S, cap], len int32 [S]) device
+    tensors (uint32 bits; len 0 = unreachable, -1 = longer than cap)."""
+    from ._lib import check, load
+    S, n = parent.shape
+    tgt = np.ascontiguousarray(targets, np.uint32).ravel()
+    if len(tgt) != S:
+        raise ValueError("extract_paths_device: one target per search")
+    dev = parent.device
+    tt = _u32_tensor(torch, tgt if S else np.zeros(1, np.uint32), dev)
+    idx = torch.zeros((S, max(int(cap), 1)), dtype=torch.int32, device=dev)
+    ln = torch.zeros(max(S, 1), dtype=torch.int32, device=dev)
+    check(load().vgpu_roadmap_extract_paths(ctx.h, parent.data_ptr(), n, tt.data_ptr(), S, int(cap), idx.data_ptr(),
+                                            ln.data_ptr()), ctx.h)
+    return idx[:, :int(cap)], ln[:S]
+
+
+def sssp_stats(ctx) -> dict:
+    """vgpu_roadmap_sssp_stats: the last sssp or bottleneck call on ctx"""
+    import ctypes as C
+
+    from ._lib import check, load
+    s = (C.c_uint64 * 4)()
+    check(load().vgpu_roadmap_sssp_stats(ctx.h, s), ctx.h)
+    return {"rounds": int(s[0]), "relaxed_slots": int(s[1]), "frontier_items": int(s[2]), "host_reads": int(s[3])}
+
+
+def _csr_host(offsets, adj):
+    off = np.ascontiguousarray(offsets).astype(np.uint64)
+    a = np.ascontiguousarray(adj, np.uint32)
+    if len(off) == 0:
+        raise ValueError("offsets holds n + 1 entries")
+    return off, (a if len(a) else np.zeros(1, np.uint32))
+
+
+def cpu_sssp(offsets, adj, w, sources, limits=None, parents: bool = True):
+    """vgpu_cpu_roadmap_sssp on host arrays: (g float32 [S, n], hops uint32 [S, n], parent uint32 [S, n]) --
+    the binary-heap Dijkstra, tight-edge BFS and parent rule the GPU search is pinned to."""
+    import ctypes as C
+
+    from . import _lib
+    from ._lib import check, load
+    off, a = _csr_host(offsets, adj)
+    n = len(off) - 1
+    wv = np.ascontiguousarray(w, np.float32)
+    wv = wv if len(wv) else np.zeros(1, np.float32)
+    src = np.ascontiguousarray(sources, np.uint32).ravel()
+    S = len(src)
+    lim = None if limits is None else np.ascontiguousarray(limits, np.uint32).ravel()
+    g = np.empty((S, n), np.float32)
+    hops = np.empty((S, n), np.uint32) if parents else None
+    parent = np.empty((S, n), np.uint32) if parents else None
+    p = lambda x, t: None if x is None else x.ctypes.data_as(t)  # noqa: E731
+    check(load().vgpu_cpu_roadmap_sssp(n, off.ctypes.data_as(_lib.U64P), p(a, _lib.U32P), p(wv, _lib.F32P),
+                                       p(src if S else np.zeros(1, np.uint32), _lib.U32P), p(lim, _lib.U32P), S,
+                                       p(g if g.size else np.zeros(1, np.float32), _lib.F32P),
+                                       p(hops if hops is None or hops.size else np.zeros(1, np.uint32), _lib.U32P),
+                                       p(parent if parent is None or parent.size else np.zeros(1, np.uint32), _lib.U32P)))
+    return g, hops, parent
+
+
+def cpu_bottleneck(offsets, adj, sources):
+    """vgpu_cpu_roadmap_bottleneck on host arrays: b uint32 [S, n] (union-find over the vertices in index order)."""
+    from . import _lib
+    from ._lib import check, load
+    off, a = _csr_host(offsets, adj)
+    n = len(off) - 1
+    src = np.ascontiguousarray(sources, np.uint32).ravel()
+    S = len(src)
+    b = np.empty((S, n), np.uint32)
+    check(load().vgpu_cpu_roadmap_bottleneck(n, off.ctypes.data_as(_lib.U64P), a.ctypes.data_as(_lib.U32P),
+                                             (src if S else np.zeros(1, np.uint32)).ctypes.data_as(_lib.U32P), S,
+                                             (b if b.size else np.zeros(1, np.uint32)).ctypes.data_as(_lib.U32P)))
+    return b
+
+
+def walk_parents(parent_row, target: int):
+    """The host form of vgpu_roadmap_extract_paths for one search: vertex indices source first, [] if the
+    target is unreachable; raises if the walk does not end within n steps."""
+    n = len(parent_row)
+    if parent_row[target] == 0xffffffff:
+        return []
+    path, v = [int(target)], int(target)
+    while int(parent_row[v]) != v:
+        v = int(parent_row[v])
+        path.append(v)
+        if len(path) > n:
+            raise RuntimeError("walk_parents: the parent chain does not end")
+    return path[::-1]
+
 
 def build_roadmap_edges(robot, environment, vertices, gamma_scale: float = 2.0, space_measure=None,
                         ctx=None) -> Roadmap:
