@@ -394,6 +394,37 @@ int vgpu_cpu_rrtc(const vgpu_robot *robot, vgpu_env *env, const float *start, co
                   const vgpu_rrtc_settings *settings, uint64_t *rng_index, float *path, size_t path_cap,
                   vgpu_plan_result *result);
 
+/* ---- batched RRT-Connect on the GPU (mr-vamp_amd/csrc/vgpu_rrtc.hip) ------------------------------ */
+/* per-problem outcome: DONE = vgpu_cpu_rrtc's result; CAPACITY = the search stopped unsolved because the tree
+ * reached node_cap while settings->max_samples is larger (the result of a CPU run with max_samples =
+ * node_cap); PATH_CAPACITY = solved, but the path is longer than path_cap (path_len set, no waypoints
+ * written -- also a direct start -> goal connection with path_cap < 2) */
+enum { VGPU_RRTC_DONE = 0, VGPU_RRTC_CAPACITY = 1, VGPU_RRTC_PATH_CAPACITY = 2 };
+/* vgpu_cpu_rrtc for P problems in one environment, one wave per problem: the whole search (sampling, nearest
+ * neighbours, the collision checks, path extraction) runs on the device, and each problem's path, cost,
+ * iterations, tree sizes and advanced rng_index equal vgpu_cpu_rrtc's bit for bit.  The Panda at any base,
+ * environments without an attachment; anything else: VGPU_ERR_UNSUPPORTED.  Device pointers:
+ * starts[P][dim], goals[P][n_goals][dim], rng_index[P] in and out (every entry >= 1), paths[P][path_cap][dim]
+ * and path_len[P] out -- the waypoints / len layout of vgpu_simplify_paths --, results[P] out (nanoseconds =
+ * 0), status[P] out (VGPU_RRTC_*, may be NULL).  Each problem's trees live in an arena of node_cap nodes: the
+ * sample limit is min(settings->max_samples, node_cap); 1 + n_goals <= node_cap, P * node_cap < 2^31.
+ * A launch advances every unfinished problem by at most `slice` iterations (vgpu_rrtc_set_slice, default
+ * 256); the host synchronises once per launch and relaunches while problems are working. */
+int vgpu_rrtc_batch(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *env, const float *starts, const float *goals,
+                    size_t n_goals, size_t P, const vgpu_rrtc_settings *settings, uint64_t *rng_index,
+                    size_t node_cap, float *paths, size_t path_cap, uint32_t *path_len, vgpu_plan_result *results,
+                    uint8_t *status);
+/* host pointers: copy in, run, copy out, synchronise */
+int vgpu_rrtc_batch_host(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *env, const float *starts,
+                         const float *goals, size_t n_goals, size_t P, const vgpu_rrtc_settings *settings,
+                         uint64_t *rng_index, size_t node_cap, float *paths, size_t path_cap, uint32_t *path_len,
+                         vgpu_plan_result *results, uint8_t *status);
+/* iterations per problem and launch of the context's later vgpu_rrtc_batch calls (0: the default, 256) */
+int vgpu_rrtc_set_slice(vgpu_ctx *ctx, uint32_t slice);
+/* counters of the context's last vgpu_rrtc_batch call: out[0] launches, out[1] iterations summed over the
+ * problems, out[2] the largest iteration count of one problem */
+int vgpu_rrtc_stats(const vgpu_ctx *ctx, uint64_t out[3]);
+
 /* ---- path simplification (planning/simplify.hh:192-260) ------------------------------------------ */
 /* vamp::planning::SimplifyRoutine (planning/simplify_settings.hh:7-13) */
 enum { VGPU_SIMPLIFY_BSPLINE = 0, VGPU_SIMPLIFY_REDUCE = 1, VGPU_SIMPLIFY_SHORTCUT = 2, VGPU_SIMPLIFY_PERTURB = 3 };

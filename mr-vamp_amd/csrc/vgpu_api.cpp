@@ -28,6 +28,7 @@
 #include "vgpu_ops.hh"
 #include "vgpu_roadmap_query.hh"
 #include "vgpu_simplify.hh"
+#include "vgpu_rrtc.hh"
 #include "gen/radii.inc"
 
 extern "C" {
@@ -295,6 +296,12 @@ struct vgpu_ctx {
     size_t simp_bytes = 0;
     uint32_t* simp_host = nullptr;
     uint64_t simp_stats[3] = {0, 0, 0};
+    // batched RRT-Connect (vgpu_rrtc.hip): the arena, the pinned launch totals, the slice, the last call's counters
+    void* rrtc = nullptr;
+    size_t rrtc_bytes = 0;
+    unsigned long long* rrtc_host = nullptr;
+    uint32_t rrtc_slice = 256;
+    uint64_t rrtc_stats[3] = {0, 0, 0};
     // roadmap queries (vgpu_roadmap_query.hip): frontier workspace, the pinned round total, the last call's counters
     vgpu::QueryState rq;
     // optional phase timing
@@ -459,6 +466,8 @@ extern "C" void vgpu_ctx_destroy(vgpu_ctx* c)
     if (c->dbg) (void)hipFree(c->dbg);
     if (c->simp) (void)hipFree(c->simp);
     if (c->simp_host) (void)hipHostFree(c->simp_host);
+    if (c->rrtc) (void)hipFree(c->rrtc);
+    if (c->rrtc_host) (void)hipHostFree(c->rrtc_host);
     vgpu::query_free(c->rq);
     if (c->tick) (void)hipFree(c->tick);
     if (c->total_host) (void)hipHostFree(c->total_host);
@@ -2641,6 +2650,157 @@ try {
     if (iterations) HIPCHK(c, hipMemcpyAsync(iterations, itd, n_paths * 4, hipMemcpyDeviceToHost, c->cur));
     if (status) HIPCHK(c, hipMemcpyAsync(status, sd, n_paths, hipMemcpyDeviceToHost, c->cur));
     if (cost) HIPCHK(c, hipMemcpyAsync(cost, cd, n_paths * 4, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipStreamSynchronize(c->cur));
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+// ---- batched RRT-Connect (planning/rrtc.hh:33-248; the kernel in vgpu_rrtc.hip) --------------------------------
+static int rrtc_sizes(vgpu_ctx* c, size_t n_goals, size_t P, size_t node_cap, size_t path_cap)
+{
+    if (n_goals == 0) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: n_goals must be at least 1");
+    if (P >= ((size_t)1 << 31) || node_cap >= ((size_t)1 << 31) || (P && node_cap > (((size_t)1 << 31) - 1) / P))
+        return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: P * node_cap must be below 2^31 (split the batch)");
+    if (n_goals >= node_cap) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: node_cap must hold the start and the goals");
+    if (path_cap >= ((size_t)1 << 31) || (P && path_cap > (((size_t)1 << 31) - 1) / P))
+        return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: P * path_cap must be below 2^31 (split the batch)");
+    return VGPU_OK;
+}
+
+// Launches until no problem is working: one slice of every unfinished problem, then ONE synchronisation and
+// read of the pinned totals.  Nothing else crosses to the host while problems run.
+extern "C" int vgpu_rrtc_batch(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, const float* starts, const float* goals,
+                               size_t n_goals, size_t P, const vgpu_rrtc_settings* settings, uint64_t* rng_index,
+                               size_t node_cap, float* paths, size_t path_cap, uint32_t* path_len,
+                               vgpu_plan_result* results, uint8_t* status)
+try {
+    if (!c || !e || e->ctx != c) return fail(c, VGPU_ERR_INVALID_ARG, "bad context/environment");
+    float b[3];
+    int rc = check_robot(c, r, b);
+    if (rc) return rc;
+    if (r->kind != VGPU_ROBOT_PANDA) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch: the Panda only");
+    if (e->attached) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch: no attachments");
+    if (!settings) return fail(c, VGPU_ERR_INVALID_ARG, "null settings");
+    c->rrtc_stats[0] = c->rrtc_stats[1] = c->rrtc_stats[2] = 0;
+    if (P == 0) return VGPU_OK;
+    if ((rc = rrtc_sizes(c, n_goals, P, node_cap, path_cap))) return rc;
+    if (!starts || !goals || !rng_index || !path_len || !results || (path_cap && !paths))
+        return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    if ((rc = vgpu_env_upload(e))) return rc;
+    const EnvView v = make_view(e);
+    HIPCHK(c, ctx_device(c));
+    const size_t slots = P * node_cap;
+    const size_t nb = al(slots * 7 * 4), pb = al(slots * 4), tb = al(slots), cb = al(P * vgpu::kRrtcWords * 4);
+    const size_t need = nb + 2 * pb + tb + cb + 256;
+    if (need > c->rrtc_bytes) {
+        if (c->rrtc) {
+            HIPCHK(c, hipStreamSynchronize(c->cur));
+            HIPCHK(c, hipFree(c->rrtc));
+            c->rrtc = nullptr;
+            c->rrtc_bytes = 0;
+        }
+        HIPCHK(c, hipMalloc(&c->rrtc, need));
+        c->rrtc_bytes = need;
+    }
+    if (!c->rrtc_host)
+        HIPCHK(c, hipHostMalloc((void**)&c->rrtc_host, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+    char* p = (char*)c->rrtc;
+    vgpu::RrtcArgs a{};
+    a.starts = starts;
+    a.goals = goals;
+    a.rng = rng_index;
+    a.nodes = (float*)p;
+    a.parent = (uint32_t*)(p + nb);
+    a.radius = (float*)(p + nb + pb);
+    a.tree = (uint8_t*)(p + nb + 2 * pb);
+    a.ctl = (uint32_t*)(p + nb + 2 * pb + tb);
+    unsigned long long* totals = (unsigned long long*)(p + nb + 2 * pb + tb + cb);
+    a.paths = paths;
+    a.path_len = path_len;
+    a.results = results;
+    a.status = status;
+    a.P = (uint32_t)P;
+    a.n_goals = (uint32_t)n_goals;
+    a.node_cap = (uint32_t)node_cap;
+    a.path_cap = (uint32_t)path_cap;
+    a.max_nodes = (uint32_t)std::min<uint64_t>(settings->max_samples, node_cap);
+    a.cap_limited = node_cap < settings->max_samples ? 1u : 0u;
+    a.slice = c->rrtc_slice;
+    a.max_iterations = settings->max_iterations;
+    a.range = settings->range;
+    a.radius0 = settings->radius;
+    a.alpha = settings->alpha;
+    a.min_radius = settings->min_radius;
+    a.tree_ratio = settings->tree_ratio;
+    a.dynamic_domain = settings->dynamic_domain;
+    a.balance = settings->balance;
+    a.start_tree_first = settings->start_tree_first;
+    a.bx = b[0];
+    a.by = b[1];
+    a.bz = b[2];
+    HIPCHK(c, hipMemsetAsync(a.ctl, 0, cb + 256, c->cur));  // every problem RPH_NEW, the totals zero
+    for (;;) {
+        HIPCHK(c, vgpu_launch_rrtc(&a, &v, totals, c->rrtc_host, c->cur));
+        HIPCHK(c, hipStreamSynchronize(c->cur));
+        if (c->rrtc_host[3]) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: rng_index entries must be at least 1");
+        c->rrtc_stats[0] += 1;
+        c->rrtc_stats[1] = c->rrtc_host[1];
+        c->rrtc_stats[2] = c->rrtc_host[2];
+        if (!c->rrtc_host[0]) break;
+    }
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_rrtc_set_slice(vgpu_ctx* c, uint32_t slice)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    c->rrtc_slice = slice ? slice : 256;
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_rrtc_stats(const vgpu_ctx* c, uint64_t out[3])
+try {
+    if (!c || !out) return VGPU_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k) out[k] = c->rrtc_stats[k];
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+extern "C" int vgpu_rrtc_batch_host(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, const float* starts,
+                                    const float* goals, size_t n_goals, size_t P, const vgpu_rrtc_settings* settings,
+                                    uint64_t* rng_index, size_t node_cap, float* paths, size_t path_cap,
+                                    uint32_t* path_len, vgpu_plan_result* results, uint8_t* status)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    float b[3];
+    int rc = check_robot(c, r, b);
+    if (rc) return rc;
+    if (r->kind != VGPU_ROBOT_PANDA) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch: the Panda only");
+    if (P == 0) return VGPU_OK;
+    if ((rc = rrtc_sizes(c, n_goals, P, node_cap, path_cap))) return rc;
+    if (!starts || !goals || !rng_index || !path_len || !results || (path_cap && !paths))
+        return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    char* d;
+    const size_t dim = dim_of(r);
+    const size_t sbytes = P * dim * 4, gbytes = P * n_goals * dim * 4, wbytes = P * path_cap * dim * 4;
+    const size_t sb = al(sbytes), gb = al(gbytes), ib = al(P * 8), wb = al(wbytes), lb = al(P * 4),
+                 rb = al(P * sizeof(vgpu_plan_result));
+    if ((rc = stage(c, sb + gb + ib + wb + lb + rb + al(P), &d))) return rc;
+    float* sd = (float*)d;
+    float* gd = (float*)(d + sb);
+    uint64_t* id = (uint64_t*)(d + sb + gb);
+    float* wd = (float*)(d + sb + gb + ib);
+    uint32_t* ld = (uint32_t*)(d + sb + gb + ib + wb);
+    vgpu_plan_result* rd = (vgpu_plan_result*)(d + sb + gb + ib + wb + lb);
+    uint8_t* std_ = (uint8_t*)(d + sb + gb + ib + wb + lb + rb);
+    HIPCHK(c, hipMemcpyAsync(sd, starts, sbytes, hipMemcpyHostToDevice, c->cur));
+    HIPCHK(c, hipMemcpyAsync(gd, goals, gbytes, hipMemcpyHostToDevice, c->cur));
+    HIPCHK(c, hipMemcpyAsync(id, rng_index, P * 8, hipMemcpyHostToDevice, c->cur));
+    if ((rc = vgpu_rrtc_batch(c, r, e, sd, gd, n_goals, P, settings, id, node_cap, wd, path_cap, ld, rd, std_)))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(rng_index, id, P * 8, hipMemcpyDeviceToHost, c->cur));
+    if (wbytes) HIPCHK(c, hipMemcpyAsync(paths, wd, wbytes, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipMemcpyAsync(path_len, ld, P * 4, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipMemcpyAsync(results, rd, P * sizeof(vgpu_plan_result), hipMemcpyDeviceToHost, c->cur));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, std_, P, hipMemcpyDeviceToHost, c->cur));
     HIPCHK(c, hipStreamSynchronize(c->cur));
     return VGPU_OK;
 } VGPU_ABI_CATCH

@@ -622,6 +622,13 @@ class PRMSettings:
         return self.neighbor_params.neighbor_radius(num_states)
 
 
+# vgpu_plan_result as a numpy record (the C layout: _lib.VgpuPlanResult)
+_PLAN_RESULT_DTYPE = np.dtype({"names": ["solved", "iterations", "nanoseconds", "size", "cost", "path_len"],
+                               "formats": ["<i4", "<u8", "<i8", ("<u8", (2,)), "<f4", "<u8"],
+                               "offsets": [0, 8, 16, 24, 40, 48], "itemsize": 56})
+assert C.sizeof(_lib.VgpuPlanResult) == _PLAN_RESULT_DTYPE.itemsize
+
+
 class PlanningResult:
     """vamp::planning::PlanningResult (planning/plan.hh): path, cost, iterations, size, nanoseconds."""
 
@@ -898,6 +905,79 @@ class Robot:
         s = (C.c_uint64 * 3)()
         check(load().vgpu_simplify_stats(ctx.h, s), ctx.h)
         return {"rounds": int(s[0]), "validate_calls": int(s[1]), "edges": int(s[2])}
+
+    # per-problem outcome of rrtc_batch / rrtc_device (VGPU_RRTC_*)
+    RRTC_DONE, RRTC_CAPACITY, RRTC_PATH_CAPACITY = 0, 1, 2
+
+    def rrtc_batch(self, starts, goals, environment: Environment, settings: Optional[RRTCSettings] = None,
+                   rng_first=1, node_cap: int = 4096, path_cap: int = 256, ctx: Optional[Context] = None,
+                   slice: Optional[int] = None):
+        """rrtc() of P start/goal problems in one environment on the GPU, one wave per problem
+        (vgpu_rrtc_batch_host): starts [P][dim], goals [P][dim] or [P][n_goals][dim], rng_first the 1-based
+        index of each problem's first Halton draw (a scalar, or one per problem).  Returns ([PlanningResult],
+        status uint8[P], the advanced indices uint64[P]); each result equals rrtc()'s bit for bit for a sampler
+        at rng_first (nanoseconds is 0).  node_cap bounds each problem's trees: the sample limit is
+        min(settings.max_samples, node_cap), and a problem that stops there unsolved has status RRTC_CAPACITY.
+        A path longer than path_cap has status RRTC_PATH_CAPACITY: its result carries `path_len` and an empty
+        path.  slice: iterations per problem and launch (default 256)."""
+        ctx = ctx or context()
+        dim = self.dimension()
+        settings = settings or RRTCSettings()
+        s = np.ascontiguousarray(starts, np.float32).reshape(-1, dim)
+        n = s.shape[0]
+        if n == 0:
+            return [], np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        g = np.ascontiguousarray(goals, np.float32).reshape(n, -1, dim)
+        idx = np.array(np.broadcast_to(np.asarray(rng_first, np.uint64), (n,)))  # a copy: advanced in place
+        node_cap, path_cap = int(node_cap), int(path_cap)
+        paths = np.zeros((n, path_cap, dim), np.float32)
+        ln = np.zeros(n, np.uint32)
+        res = (_lib.VgpuPlanResult * n)()
+        st = np.zeros(n, np.uint8)
+        cs = settings.c()
+        if slice is not None:
+            check(load().vgpu_rrtc_set_slice(ctx.h, int(slice)), ctx.h)
+        try:
+            check(load().vgpu_rrtc_batch_host(ctx.h, C.byref(self.c_robot), environment.handle(ctx),
+                                              s.ctypes.data_as(_lib.F32P), g.ctypes.data_as(_lib.F32P), g.shape[1], n,
+                                              C.byref(cs), idx.ctypes.data_as(_lib.U64P), node_cap,
+                                              paths.ctypes.data_as(_lib.F32P), path_cap, ln.ctypes.data_as(_lib.U32P),
+                                              res, st.ctypes.data_as(_lib.U8P)), ctx.h)
+        finally:
+            if slice is not None:
+                load().vgpu_rrtc_set_slice(ctx.h, 0)
+        # the records as arrays: one pass over a structured view instead of ctypes field reads per problem
+        rec = np.frombuffer(res, dtype=_PLAN_RESULT_DTYPE)
+        solved, its, cost = rec["solved"].tolist(), rec["iterations"].tolist(), rec["cost"].tolist()
+        sizes, lens, stl = rec["size"].tolist(), ln.tolist(), st.tolist()
+        out = []
+        for i in range(n):
+            kept = lens[i] if stl[i] != self.RRTC_PATH_CAPACITY else 0
+            pr = PlanningResult(paths[i, :kept].copy(), cost[i], its[i], (sizes[i][0], sizes[i][1]), 0, bool(solved[i]))
+            pr.status, pr.path_len = stl[i], lens[i]
+            out.append(pr)
+        return out, st, idx
+
+    def rrtc_device(self, starts_ptr: int, goals_ptr: int, n_goals: int, n_problems: int, environment: Environment,
+                    settings: Optional[RRTCSettings], rng_index_ptr: int, node_cap: int, paths_ptr: int, path_cap: int,
+                    path_len_ptr: int, results_ptr: int, status_ptr: int = 0, ctx: Optional[Context] = None):
+        """vgpu_rrtc_batch over device memory: starts float32 [P][dim], goals [P][n_goals][dim], rng_index uint64
+        [P] in place, paths float32 [P][path_cap][dim] and path_len uint32 [P] out -- simplify_device's waypoints
+        and len --, results [P] vgpu_plan_result records (56 bytes each), status uint8 [P] optional."""
+        ctx = ctx or context()
+        cs = (settings or RRTCSettings()).c()
+        check(load().vgpu_rrtc_batch(ctx.h, C.byref(self.c_robot), environment.handle(ctx), C.c_void_p(starts_ptr),
+                                     C.c_void_p(goals_ptr), int(n_goals), int(n_problems), C.byref(cs),
+                                     C.c_void_p(rng_index_ptr), int(node_cap), C.c_void_p(paths_ptr), int(path_cap),
+                                     C.c_void_p(path_len_ptr), C.c_void_p(results_ptr), C.c_void_p(status_ptr or 0)),
+              ctx.h)
+
+    def rrtc_stats(self, ctx: Optional[Context] = None) -> dict:
+        """counters of the context's last rrtc_batch / rrtc_device call"""
+        ctx = ctx or context()
+        s = (C.c_uint64 * 3)()
+        check(load().vgpu_rrtc_stats(ctx.h, s), ctx.h)
+        return {"launches": int(s[0]), "iterations": int(s[1]), "max_iterations": int(s[2])}
 
     def roadmap(self, start, goal, environment: Environment, settings: Optional[PRMSettings] = None,
                 rng: Optional[Halton] = None, ctx: Optional[Context] = None):
