@@ -5,7 +5,12 @@ Its edge checks are the oracle's validate_vector (oracle/vamp_oracle.c), its sam
 Halton closed form + scale_configuration, its nearest neighbours a numpy scan in float32 with
 FloatVector::l2_norm's lane order (nn.hh:53-57).  Both restate the same source independently, so
 equal paths, costs, iterations and tree sizes pin the product's planner logic (the reference
-itself cannot be compiled here: nigh is absent)."""
+itself cannot be compiled here: nigh is absent).
+
+rrtc(trace={}) counts the branches a search takes (tests/rrtc_cases.py EVENTS), named for what they mean to the
+batched GPU planner (mr-vamp_amd/csrc/vgpu_rrtc.hip): rake blocks per segment, segments packed into a pass of 8
+groups, where in a pass a connect fails or is cut by the sample limit, the dynamic-domain branches, trees wider
+than a wave, ties of the nearest-neighbour scan."""
 import numpy as np
 
 import oracle_py as op
@@ -50,7 +55,15 @@ def l2_rows(d):
     return np.sqrt(a + b).astype(F)
 
 
-def rrtc(robot, oenv, start, goals, settings, rng_index, base100=(0, 0, 0)):
+def blocks_of(distance):
+    """validate_vector's block count from the caller's distance (validate.hh:41), in float32"""
+    return max(int(np.ceil(F(F(F(distance) / F(8)) * F(32)))), 1)
+
+
+def rrtc(robot, oenv, start, goals, settings, rng_index, base100=(0, 0, 0), trace=None, tie_last=False):
+    """trace: a dict that receives event counters (the branches a search took; tests/rrtc_cases.py lists them).
+    tie_last: among equal nearest distances take the LAST-inserted node -- not the planner's rule; it exists so
+    that a test can show that a case with a tie depends on the rule."""
     S = dict(range=2.0, dynamic_domain=True, radius=4.0, alpha=0.0001, min_radius=1.0, balance=True,
              tree_ratio=1.0, max_iterations=100000, max_samples=100000, start_tree_first=True)
     S.update(settings)
@@ -86,10 +99,23 @@ def rrtc(robot, oenv, start, goals, settings, rng_index, base100=(0, 0, 0)):
     tree_a_is_start = not S["start_tree_first"]
     ta, tb = (goal_tree, start_tree) if S["start_tree_first"] else (start_tree, goal_tree)
 
+    def ev(name):
+        if trace is not None:
+            trace[name] = trace.get(name, 0) + 1
+
     def nearest(tree, q):
         C = np.stack([buf[i] for i in tree])
         d = l2_rows((q[None, :] - C).astype(F))
         k = int(np.argmin(d))
+        same = np.nonzero(d == d[k])[0]  # the bitwise minimum (no -0: distances are square roots)
+        if len(same) > 1:
+            ev("tie")
+            if tie_last:
+                k = int(same[-1])
+        if len(tree) > 64:
+            ev("nn_over_64")
+        if tree[k] >= 64:
+            ev("nn_winner_over_64")
         return tree[k], d[k]
 
     it = 0
@@ -109,15 +135,19 @@ def rrtc(robot, oenv, start, goals, settings, rng_index, base100=(0, 0, 0)):
         nn, nd = nearest(ta, temp)
         nr = radii[nn]
         if S["dynamic_domain"] and nr < nd:
+            ev("dd_reject")
             continue
         nc = buf[nn]
         v = (temp - nc).astype(F)
         reach = nd < rng_f
         ext = v if reach else (v * (rng_f / nd)).astype(F)
+        ev("ext_reach" if reach else "ext_clip")
+        ev(f"ext_n={blocks_of(nd if reach else rng_f)}")
         if vv(nc, ext, nd if reach else rng_f):
             newc = (nc + ext).astype(F)
             ta.append(push(newc, nn))
             if S["dynamic_domain"] and nr != FMAX:
+                ev("dd_grow")
                 radii[nn] = F(radii[nn] * (F(1) + F(S["alpha"])))
             on, od = nearest(tb, newc)
             onv = (buf[on] - newc).astype(F)
@@ -126,12 +156,30 @@ def rrtc(robot, oenv, start, goals, settings, rng_index, base100=(0, 0, 0)):
             inc = (onv * (F(1) / F(n_ext))).astype(F) if n_ext else onv
             prior = newc
             i = 0
-            while i < n_ext and vv(prior, inc, inc_len) and len(buf) < S["max_samples"]:
+            blocks = blocks_of(inc_len) if n_ext else 1
+            per = max(8 // blocks, 1)  # segments that share one pass of the wave's 8 rake groups
+            if n_ext:
+                ev(f"con_n={blocks}")
+                if blocks <= 8 and n_ext > per:
+                    ev("con_multi_pass_packed")
+            else:
+                ev("con_n_ext_0")
+            while i < n_ext:
+                if not vv(prior, inc, inc_len):
+                    ev("con_fail_first_in_pass" if blocks > 8 or i % per == 0 else "con_fail_later_in_pass")
+                    break
+                if not len(buf) < S["max_samples"]:
+                    ev("con_cut_by_cap")
+                    if blocks <= 8 and i % per:
+                        ev("con_cut_inside_pass")  # the cut falls between two segments of one pass
+                    break
                 nxt = (prior + inc).astype(F)
                 ta.append(push(nxt, len(buf) - 1))
                 prior = nxt
                 i += 1
             if i == n_ext:
+                ev("solved_noflip" if tree_a_is_start else "solved_flip")
+                ev("len_b_0" if parents[on] == on else "len_b_pos")
                 cur = len(buf) - 1
                 path = [buf[cur]]
                 while parents[cur] != cur:
@@ -148,7 +196,8 @@ def rrtc(robot, oenv, start, goals, settings, rng_index, base100=(0, 0, 0)):
                     path.reverse()
                 break
         elif S["dynamic_domain"]:
-            radii[nn] = F(S["radius"]) if nr == FMAX else max(F(radii[nn] * (F(1) - F(S["alpha"]))),
-                                                              F(S["min_radius"]))
+            shrunk = F(radii[nn] * (F(1) - F(S["alpha"])))
+            ev("dd_first_shrink" if nr == FMAX else "dd_clamp" if shrunk < F(S["min_radius"]) else "dd_shrink")
+            radii[nn] = F(S["radius"]) if nr == FMAX else max(shrunk, F(S["min_radius"]))
     sizes = (len(start_tree), len(goal_tree))
     return (np.stack(path) if path else np.zeros((0, dim), F)), cost, it, sizes, rng_index

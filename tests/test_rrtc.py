@@ -7,12 +7,18 @@ Checks: the straight start -> goal validate_motion of each problem equals the re
 the product planner equals an independent Python restatement (tests/rrtc_py.py, oracle
 validate_vector) path for path, bit for bit, with the same iterations, tree sizes and cost; every
 solved path starts at the start, ends at the goal (to the last increment), and each of its segments passes validate_motion
-(oracle) or is one of the planner's own validate_vector-checked extensions."""
+(oracle) or is one of the planner's own validate_vector-checked extensions.
+
+The same equality holds on every case of tests/rrtc_cases.py -- the settings, goals, bases and scenes at which
+tests/test_gpu_rrtc_batch.py compares the GPU batch with this planner --, at the exact sample limits, and on goals
+constructed to tie in the nearest-neighbour scan; the restatement's trace shows which branches the table takes."""
 import numpy as np
 import pytest
 
+import rrtc_cases as rc
 import rrtc_py
 from conftest import host_fixture
+from rrtc_cases import problem  # noqa: F401  (tests/test_gpu_rrtc_batch.py imports it from here)
 from test_gpu_parity import gpu_env_from_oracle
 from test_oracle import EDGE_MIN_COVERAGE, MARGIN_TEST, fixture_check, same_rsqrt_host, stable
 
@@ -24,13 +30,6 @@ SETTINGS = dict(range=1.0, max_iterations=1000000, max_samples=1000000)
 def vamp():
     import vamp_amd
     return vamp_amd
-
-
-def problem(oracle, fx, k):
-    o = oracle.Env()
-    for key in ("spheres", "capsules", "zcapsules", "cuboids", "zcuboids"):
-        setattr(o, key, [list(r) for r in fx[f"p{k}_env_{key}"]])
-    return o, fx[f"p{k}_start"], fx[f"p{k}_goal"]
 
 
 def test_straight_line_vs_reference_dag(vamp, oracle):
@@ -122,6 +121,107 @@ def test_rrtc_rng_and_settings(vamp, oracle):
     blocked.add_sphere(vamp.Sphere([0.0, 0.0, 0.4], 0.6))
     r = robot.rrtc(s, g, blocked, vamp.RRTCSettings(range=1.0, max_iterations=200, max_samples=1000), robot.halton())
     assert not r.solved and r.path.shape == (0, 7) and r.iterations == 201
+
+
+# ---- the case table of tests/rrtc_cases.py: every setting at which the GPU batch is compared with this planner --------
+def planner_run(vamp, env, start, goals, settings, first, base=(0, 0, 0)):
+    robot = vamp.PandaBase(*base)
+    rng = robot.halton()
+    rng.skip(int(first) - 1)
+    return robot.rrtc(start, goals, env, vamp.RRTCSettings(**settings), rng), rng.index
+
+
+def same_as_restatement(res, idx, ref, tag):
+    """path and cost bit for bit, iterations, tree sizes, solved and the advanced sampler index; a search that ends
+    unsolved (at a bound) is compared like a solved one"""
+    p, cost, it, sizes, widx = ref
+    assert (res.solved, res.iterations, tuple(res.size), idx) == (len(p) > 0, it, sizes, widx), \
+        (tag, res.solved, res.iterations, res.size, idx, len(p), it, sizes, widx)
+    assert res.path.shape == p.shape, (tag, res.path.shape, p.shape)
+    assert np.array_equal(res.path.view(np.uint32), p.view(np.uint32)), tag
+    assert np.float32(res.cost).view(np.uint32) == np.float32(cost).view(np.uint32), (tag, res.cost, cost)
+
+
+@pytest.mark.parametrize("name", list(rc.CASES))
+def test_planner_matches_restatement_on_case(vamp, oracle, name):
+    case = rc.CASES[name]
+    want, _ = rc.restated(name)
+    for b in range(len(case.batches)):
+        k, starts, goals, firsts = case.arrays(b)
+        env = rc.vamp_env(vamp, k, case.cloud)
+        for i in range(len(starts)):
+            res, idx = planner_run(vamp, env, starts[i], goals[i], case.settings, firsts[i], case.base)
+            same_as_restatement(res, idx, want[b][i], (name, k, i))
+
+
+def test_case_table_reaches_every_branch(oracle):
+    """Conditions of the case table, read from the restatement's trace alone: the table takes every branch the
+    GPU planner distinguishes -- block counts per segment that leave rake groups idle (3, 5, 6, 7), fill a pass
+    (8), need two passes (9 .. 16) and three (17, 18), packed connects over several passes, failures at the
+    head of a pass and behind valid segments, every dynamic-domain branch, both path orientations, trees wider
+    than a wave.  Not counted: a failure in the second or later pass of one segment (the oracle's
+    validate_vector does not report the failing block)."""
+    t = {}
+    for name in rc.CASES:
+        for key, v in rc.restated(name)[1].items():
+            t[key] = t.get(key, 0) + v
+    print("merged trace:", sorted(t.items()))
+    known = {e for e in rc.EVENTS if "=" not in e}
+    assert all(key in known or key.split("=")[0] in ("ext_n", "con_n") for key in t), sorted(t)
+    for key in ("dd_reject", "dd_first_shrink", "dd_shrink", "dd_clamp", "dd_grow"):
+        assert t.get(key, 0) >= 10, (key, t.get(key, 0))
+    for key in ("ext_reach", "ext_clip", "con_multi_pass_packed", "con_fail_first_in_pass", "con_fail_later_in_pass",
+                "con_cut_by_cap", "solved_flip", "solved_noflip", "len_b_0", "len_b_pos", "nn_over_64",
+                "nn_winner_over_64"):
+        assert t.get(key, 0) >= 1, key
+    ext = {int(key[6:]) for key in t if key.startswith("ext_n=")}
+    con = {int(key[6:]) for key in t if key.startswith("con_n=")}
+    assert {1, 2, 3, 4, 6, 9} <= ext and max(ext) >= 17, sorted(ext)
+    assert set(range(1, 10)) <= con and con & set(range(10, 17)), sorted(con)
+    assert "con_n_ext_0" not in t  # a new node bitwise equal to a node of the other tree: not constructed
+
+
+@pytest.mark.parametrize("name", list(rc.LIMITS))
+def test_exact_limits(vamp, oracle, name):
+    """the sample limit at the node count N of a solved search and one below: the planner equals the restatement
+    at both; N solves, N - 1 stops in the last connect -- in `packed` between two segments of one pass"""
+    settings, k, first = rc.LIMITS[name]
+    o, s, g = rc.scene(k)
+    env = rc.vamp_env(vamp, k)
+    free, idx = planner_run(vamp, env, s, g, settings, first)
+    assert free.solved
+    same_as_restatement(free, idx, rrtc_py.rrtc("panda", o, s, g, settings, first), (name, "free"))
+    N = sum(free.size)
+    for limit in (N, N - 1):
+        cut = dict(settings, max_samples=limit)
+        trace = {}
+        want = rrtc_py.rrtc("panda", o, s, g, cut, first, trace=trace)
+        res, idx = planner_run(vamp, env, s, g, cut, first)
+        same_as_restatement(res, idx, want, (name, limit))
+        assert res.solved == (limit == N) and sum(res.size) == limit
+        if limit == N:
+            assert res.path.tobytes() == free.path.tobytes() and res.iterations == free.iterations
+        else:
+            assert trace.get("con_cut_by_cap") == 1
+            if name == "packed":
+                assert trace.get("con_cut_inside_pass") == 1
+
+
+# ---- the nearest-neighbour tie rule -------------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ["adjacent", "adjacent-rev", "stride", "stride-rev"])
+def test_nearest_tie_takes_the_earliest_node(vamp, oracle, layout):
+    """Two goals at bitwise equal distance from the first sample (rrtc_cases.tie_layouts): the planner takes the
+    earliest-inserted one, as the restatement's argmin does, and the search depends on it -- the restatement
+    with the opposite rule (tie_last) takes another course."""
+    goals = rc.tie_layouts()[layout]
+    _, s, _ = rc.scene(rc.TIE_PROBLEM)
+    want, trace = rc.tie_restated(layout)
+    other, _ = rc.tie_restated(layout, True)
+    assert trace.get("tie", 0) >= 1
+    assert want[2] > 1 and other[2] > 1  # no goal connects to the start directly
+    assert (want[2], want[0].tobytes()) != (other[2], other[0].tobytes())
+    res, idx = planner_run(vamp, rc.vamp_env(vamp, rc.TIE_PROBLEM), s, goals, rc.TIE_SETTINGS, 1)
+    same_as_restatement(res, idx, want, layout)
 
 
 # ---- BASELINE configs[4]'s planner half: RRT-Connect on the two-Panda composite -------------------------------
