@@ -166,6 +166,13 @@ int vgpu_env_upload(vgpu_env *env);
 int vgpu_env_upload_stats(const vgpu_env *env, uint64_t out[3]);
 /* point cloud `index`'s cell grid as the uploaded device header records it: {nx, ny, nz, cells_off} */
 int vgpu_env_pointcloud_grid(vgpu_env *env, int index, uint32_t out[4]);
+/* The environment's clearance grid as the device holds it (uploads first): per cell a lower bound, in units of
+ * hdr[17] metres, of the distance from the cell to the nearest obstacle surface beyond the margin hdr[15]; the
+ * validate kernels skip the obstacle scans of spheres it proves clear (results unchanged).  hdr = {lo xyz, cell
+ * size xyz, 1 / cell size xyz, the records' AABB lo xyz, hi xyz, margin, rounding slack, step}; *n = cells per
+ * axis, 0 when the environment has no grid (heightfields, point clouds, more than 256 or non-finite records,
+ * a sheared cuboid, VAMP_AMD_CLEAR=0).  cells (may be NULL): n^3 bytes in 4 x 4 x 4 bricks, cap = its size. */
+int vgpu_env_clear_grid(vgpu_env *env, float hdr[18], int32_t *n, uint8_t *cells, size_t cap);
 
 /* ---- batched hot path (device pointers, asynchronous) ------------------------------------ */
 /* Robot::sphere_fk for n configurations q[n][dim] -> xyz[3][n_spheres][ld] (SoA, world frame,

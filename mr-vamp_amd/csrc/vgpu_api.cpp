@@ -106,6 +106,7 @@ hipError_t vgpu_launch_mask_finish(size_t n_edges, const uint32_t* off, uint8_t*
 hipError_t vgpu_launch_tail_counts(const float* starts, const float* goals, size_t n_edges, const uint8_t* ok,
                                    int32_t* n_blocks, uint32_t* cnt, const ItemTotalArgs* tot, hipStream_t st);
 hipError_t vgpu_launch_capt_grid(float* base, const vgpu::CaptGridArgs* g, hipStream_t st);
+hipError_t vgpu_launch_clear_grid(const ClearGridArgs* g, hipStream_t st);
 hipError_t vgpu_launch_capt_query(const float* centers, const float* radii, size_t n, const EnvView* env, int index,
                                   int simd, uint8_t* out, hipStream_t st);
 hipError_t vgpu_launch_panda_sphere_fk(const float* q, size_t n, float bx, float by, float bz, float* out,
@@ -268,6 +269,8 @@ struct vgpu_ctx {
     long lead = -1;                // A/B: source kinds that run the lead pass (VAMP_AMD_LEAD), -1 = the robot's
     bool head_list = true;         // A/B: validate heads after the lead pass over its compacted list (VAMP_AMD_HEAD_LIST)
     bool no_near = false;          // A/B: children scan every culled record, no near sets (VAMP_AMD_NEAR=0)
+    bool no_clear = false;         // A/B: no clearance grid, every bounding sphere is scanned (VAMP_AMD_CLEAR=0)
+    int clear_n = 128;             // A/B: cells per axis of the clearance grid (VAMP_AMD_CLEAR_N: 64 or 128)
     uint32_t* st_list = nullptr;   // that list (edges still valid, ascending), its count word, the selection's temp
     size_t st_list_cap = 0;
     uint32_t* st_mask = nullptr;
@@ -336,6 +339,14 @@ struct vgpu_env {
     std::mutex host_mu;
     float* dev = nullptr;
     size_t dev_floats = 0;
+    // clearance grid (vgpu_clear_grid.hip): the environment's own buffer, rebuilt with every tail upload;
+    // clr_ok = false: this environment has none (see clear_grid_plan)
+    uint8_t* clr = nullptr;
+    int clr_cells = 0;  // cells per axis the buffer was allocated for
+    bool clr_ok = false;
+    float clr_lo[3] = {0, 0, 0}, clr_h[3] = {0, 0, 0}, clr_inv_h[3] = {0, 0, 0}, clr_a[6] = {0, 0, 0, 0, 0, 0};
+    float clr_margin = 0, clr_slack = 0;
+    uint64_t n_clear = 0;  // clearance grid builds
 };
 
 // A context's device made current for this thread, and the thread's last HIP error cleared: a HANDLED failure of an
@@ -386,6 +397,8 @@ try {
     if (const char* s = std::getenv("VAMP_AMD_LEAD")) c->lead = std::strtol(s, nullptr, 0);
     if (const char* s = std::getenv("VAMP_AMD_HEAD_LIST")) c->head_list = std::strcmp(s, "0") != 0;
     if (const char* s = std::getenv("VAMP_AMD_NEAR")) c->no_near = std::strcmp(s, "0") == 0;
+    if (const char* s = std::getenv("VAMP_AMD_CLEAR")) c->no_clear = std::strcmp(s, "0") == 0;
+    if (const char* s = std::getenv("VAMP_AMD_CLEAR_N")) c->clear_n = std::atoi(s) == 64 ? 64 : 128;
     if (const char* s = std::getenv("VAMP_AMD_ROUNDS")) {  // A/B: comma-separated check bit masks
         for (const char* p = s; *p;) {
             char* end = nullptr;
@@ -628,6 +641,7 @@ extern "C" void vgpu_env_destroy(vgpu_env* e)
         (void)hipSetDevice(e->ctx->device);
         (void)hipStreamSynchronize(e->ctx->cur);
         (void)hipFree(e->dev);
+        if (e->clr) (void)hipFree(e->clr);
     }
     delete e;
 }
@@ -1089,6 +1103,117 @@ static int build_blob(vgpu_env* e, std::vector<float>& blob, std::vector<std::pa
     return VGPU_OK;
 }
 
+// The clearance grid (vgpu_clear_grid.hip) of the records as the device blob holds them; called by vgpu_env_upload
+// after the tail's copy is queued, on the same stream.  An environment gets a grid when it holds only primitive
+// records (no heightfield, no point cloud), between 1 and kClrMaxRecords of them, all finite with non-negative
+// radii and half extents, every cuboid orthonormal by obstacle_bound's test (a sheared cuboid's test value is no
+// distance), and VAMP_AMD_CLEAR is not 0.  Otherwise clr_ok = false and every sphere is scanned.
+// Box: A = the AABB of all records (rounded outward); the grid covers A grown by max(0.3 m, 5 % of its extent)
+// on every side, extents below 1e-3 m widened to that, in n^3 cells of anisotropic size.  Centres outside the grid
+// are decided by their distance to A (clear_lane).
+static int clear_grid_build(vgpu_env* e)
+{
+    vgpu_ctx* c = e->ctx;
+    e->clr_ok = false;
+    const size_t total = e->spheres.size() + e->capsules.size() + e->zcapsules.size() + e->cuboids.size() +
+                         e->zcuboids.size();
+    if (c->no_clear || total == 0 || total > (size_t)kClrMaxRecords || !e->heightfields.empty() ||
+        !e->pointclouds.empty())
+        return VGPU_OK;
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    bool ok = true;
+    auto grow = [&](int i, double a, double b) {
+        lo[i] = std::min(lo[i], std::min(a, b));
+        hi[i] = std::max(hi[i], std::max(a, b));
+    };
+    auto finite_row = [&](const float* row, int nf) {
+        for (int i = 0; i < nf; ++i) ok = ok && std::isfinite(row[i]);
+    };
+    for (const auto& s : e->spheres) {
+        finite_row(s.data(), 5);
+        ok = ok && s[3] >= 0.0f;
+        for (int i = 0; i < 3; ++i) grow(i, (double)s[i] - s[3], (double)s[i] + s[3]);
+    }
+    for (int z = 0; z < 2; ++z)
+        for (const auto& k : z ? e->zcapsules : e->capsules) {
+            finite_row(k.data(), 9);
+            ok = ok && k[6] >= 0.0f;
+            for (int i = 0; i < 3; ++i) {
+                const double v = (z && i < 2) ? 0.0 : (double)k[3 + i];  // the z-capsule's test reads zv alone
+                grow(i, (double)k[i] - k[6], (double)k[i] + k[6]);
+                grow(i, (double)k[i] + v - k[6], (double)k[i] + v + k[6]);
+            }
+        }
+    for (int z = 0; z < 2; ++z)
+        for (const auto& q : z ? e->zcuboids : e->cuboids) {
+            finite_row(q.data(), 16);
+            float bound[4];
+            obstacle_bound(z ? OBS_ZCUBOID : OBS_CUBOID, q.data(), bound);
+            ok = ok && std::isfinite(bound[3]) && q[12] >= 0.0f && q[13] >= 0.0f && q[14] >= 0.0f;
+            for (int i = 0; i < 3; ++i) {
+                double ext = 0.0;  // sum over the axes of |axis_k[i]| * half extent k
+                for (int k = 0; k < 3; ++k) {
+                    double a = q[3 + 3 * k + i];
+                    if (z) a = k == 2 ? (i == 2 ? 1.0 : 0.0) : (i == 2 ? 0.0 : a);  // as the z-cuboid's test reads them
+                    ext += std::fabs(a) * (double)q[12 + k];
+                }
+                ext *= 1.0 + 1e-5;  // axes orthonormal to 1e-6
+                grow(i, (double)q[i] - ext, (double)q[i] + ext);
+            }
+        }
+    if (!ok) return VGPU_OK;
+    double scale = 0.0, maxabs = 0.0;
+    for (int i = 0; i < 3; ++i) scale = std::max(scale, hi[i] - lo[i]);
+    const double pad = std::max(0.3, 0.05 * scale);
+    const int n = c->clear_n;
+    double blo[3], bh[3];
+    for (int i = 0; i < 3; ++i) {
+        blo[i] = lo[i] - pad;
+        const double ext = std::max(hi[i] + pad - blo[i], 1e-3);
+        bh[i] = ext / n;
+        maxabs = std::max(maxabs, std::max(std::fabs(blo[i]), std::fabs(blo[i] + ext)));
+    }
+    scale += 2.0 * pad;
+    if (!(std::isfinite(scale) && std::isfinite(maxabs) && scale < 1e30 && maxabs < 1e30)) return VGPU_OK;
+    for (int i = 0; i < 3; ++i) {
+        e->clr_lo[i] = (float)blo[i];
+        e->clr_h[i] = (float)bh[i];
+        e->clr_inv_h[i] = 1.0f / e->clr_h[i];
+        // A rounded outward, so that every record lies inside the float box
+        e->clr_a[i] = std::nextafter((float)lo[i], -HUGE_VALF);
+        e->clr_a[3 + i] = std::nextafter((float)hi[i], HUGE_VALF);
+        if (!(e->clr_h[i] > 0.0f) || !std::isfinite(e->clr_inv_h[i])) return VGPU_OK;
+    }
+    e->clr_margin = (float)(1e-3 + 1e-5 * scale);
+    e->clr_slack = (float)((scale + maxabs) / 1048576.0);
+    if (!e->clr || e->clr_cells != n) {
+        if (e->clr) {
+            HIPCHK(c, hipStreamSynchronize(c->cur));
+            HIPCHK(c, hipFree(e->clr));
+            e->clr = nullptr;
+        }
+        HIPCHK(c, hipMalloc(&e->clr, (size_t)n * n * n));
+        e->clr_cells = n;
+    }
+    ClearGridArgs g{};
+    for (int t = 0; t < OBS_TYPES; ++t) {
+        g.obs[t] = (const VGPU_CONST float*)(e->dev + e->dev_lay.off[t]);
+        g.n[t] = e->dev_lay.cnt[t];
+    }
+    for (int i = 0; i < 3; ++i) {
+        g.lo[i] = e->clr_lo[i];
+        g.h[i] = e->clr_h[i];
+    }
+    g.margin = e->clr_margin;
+    g.slack = e->clr_slack;
+    g.nc = n;
+    g.out = e->clr;
+    HIPCHK(c, vgpu_launch_clear_grid(&g, c->cur));
+    e->clr_ok = true;
+    ++e->n_clear;
+    return VGPU_OK;
+}
+
 extern "C" int vgpu_env_upload(vgpu_env* e)
 try {
     if (!e) return VGPU_ERR_INVALID_ARG;
@@ -1103,6 +1228,7 @@ try {
         if (e->tail_off + tail.size() <= e->dev_floats) {
             HIPCHK(c, hipMemcpyAsync(e->dev + e->tail_off, tail.data(), tail.size() * sizeof(float),
                                      hipMemcpyHostToDevice, c->cur));
+            if (int rc = clear_grid_build(e)) return rc;
             HIPCHK(c, hipStreamSynchronize(c->cur));  // tail is a host temporary
             e->dirty = false;
             ++e->n_tail;
@@ -1141,6 +1267,7 @@ try {
             HIPCHK(c, vgpu_launch_capt_grid(e->dev, &g, c->cur));
             ++e->n_grids;
         }
+    if (int rc = clear_grid_build(e)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->cur));  // blob is a host temporary
     e->dirty = e->pc_dirty = false;
     ++e->n_full;
@@ -1169,6 +1296,37 @@ try {
     out[0] = e->n_full;
     out[1] = e->n_tail;
     out[2] = e->n_grids;
+    return VGPU_OK;
+} VGPU_ABI_CATCH
+
+// The clearance grid as the device holds it (tests): hdr = {lo xyz, h xyz, inv_h xyz, A lo xyz, A hi xyz, margin,
+// slack, step}, *n = cells per axis (0: this environment has no grid), cells = up to cap bytes in storage order
+// (4 x 4 x 4 bricks).  Uploads the environment first.
+extern "C" int vgpu_env_clear_grid(vgpu_env* e, float hdr[18], int32_t* n, uint8_t* cells, size_t cap)
+try {
+    if (!e || !e->ctx || !hdr || !n) return VGPU_ERR_INVALID_ARG;
+    if (int rc = vgpu_env_upload(e)) return rc;
+    vgpu_ctx* c = e->ctx;
+    *n = 0;
+    for (int i = 0; i < 18; ++i) hdr[i] = 0.0f;
+    if (!e->clr_ok || !e->clr) return VGPU_OK;
+    for (int i = 0; i < 3; ++i) {
+        hdr[i] = e->clr_lo[i];
+        hdr[3 + i] = e->clr_h[i];
+        hdr[6 + i] = e->clr_inv_h[i];
+    }
+    for (int i = 0; i < 6; ++i) hdr[9 + i] = e->clr_a[i];
+    hdr[15] = e->clr_margin;
+    hdr[16] = e->clr_slack;
+    hdr[17] = kClrStep;
+    *n = e->clr_cells;
+    const size_t bytes = (size_t)e->clr_cells * e->clr_cells * e->clr_cells;
+    if (cells) {
+        if (cap < bytes) return fail(c, VGPU_ERR_INVALID_ARG, "clearance grid buffer too small");
+        HIPCHK(c, ctx_device(c));
+        HIPCHK(c, hipStreamSynchronize(c->cur));
+        HIPCHK(c, hipMemcpy(cells, e->clr, bytes, hipMemcpyDeviceToHost));
+    }
     return VGPU_OK;
 } VGPU_ABI_CATCH
 
@@ -1223,6 +1381,17 @@ static EnvView make_view(const vgpu_env* e)
         total += v.n[t];
     }
     v.near_ok = (total <= kNearMax && !e->ctx->no_near) ? 1 : 0;
+    v.clr_ok = (e->clr_ok && e->clr) ? 1 : 0;
+    if (v.clr_ok) {
+        v.clr = e->clr;
+        for (int i = 0; i < 3; ++i) {
+            v.clr_lo[i] = e->clr_lo[i];
+            v.clr_inv_h[i] = e->clr_inv_h[i];
+        }
+        for (int i = 0; i < 6; ++i) v.clr_a[i] = e->clr_a[i];
+        v.clr_margin = e->clr_margin;
+        v.clr_n = e->clr_cells;
+    }
     return v;
 }
 

@@ -134,6 +134,21 @@ struct DeferTagOf<G, std::void_t<decltype(G::kDeferTag)>> {
     static constexpr bool on = true;
     static constexpr int tag = G::kDeferTag;
 };
+// Groups whose environment scans first look the sphere up in the environment's clearance grid (clear_lane
+// below): a lane the grid proves clear of every obstacle drops out of the scans, and a wave of clear lanes
+// skips them.  Primitive environments only (never combined with Deferred).
+template <class G>
+struct Cleared : G {
+    static constexpr bool kCleared = true;
+};
+template <class G, class = void>
+struct ClearOf {
+    static constexpr bool on = false;
+};
+template <class G>
+struct ClearOf<G, std::void_t<decltype(G::kCleared)>> {
+    static constexpr bool on = G::kCleared;
+};
 constexpr int kChildTag = 63;
 constexpr int kTagDefault = -2;  // env_bits: the group type's default tag
 
@@ -245,8 +260,32 @@ struct EnvView {
     // of type t is bit near_base[t] + i
     int near_ok;
     int near_base[OBS_TYPES];
+    // clearance grid (vgpu_clear_grid.hip, clear_lane below): clr_ok = 0 when the environment has none.  clr_n^3
+    // cells of size 1 / clr_inv_h from clr_lo, stored in 4 x 4 x 4 bricks (capt_cell_index); clr_a = the AABB of
+    // every record (lo xyz, hi xyz), which the grid's box contains with a pad
+    const uint8_t* clr;
+    float clr_lo[3], clr_inv_h[3];
+    float clr_a[6];
+    float clr_margin;
+    int clr_n;
+    int clr_ok;
 };
 constexpr int kNearMax = 64;
+// Clearance grid: cell value v (uint8, saturating) states that every point of the cell is farther than
+// v * kClrStep + margin from every obstacle surface; 0 = no statement.  255 steps = 0.498 m, above every robot
+// sphere's radius.  Only environments of at most kClrMaxRecords finite primitive records get one.
+constexpr float kClrStep = 1.0f / 512.0f;
+constexpr int kClrMaxRecords = 256;
+// arguments of the grid build: the records in the device layout (EnvView obs / n), the cell sizes, and the float
+// rounding slack of the centre distances (taken off every bound on top of the margin)
+struct ClearGridArgs {
+    const VGPU_CONST float* obs[OBS_TYPES];
+    int n[OBS_TYPES];
+    float lo[3], h[3];
+    float margin, slack;
+    int nc;
+    uint8_t* out;
+};
 constexpr int kAttHdr = 8;
 constexpr int kExtHdr = 32;
 // heightfield header: x y z xs ys zs xd yd xd2 yd2 (floats) | data_off cells (uint32 bits)
@@ -355,7 +394,7 @@ struct ObsRec {
 #endif
 template <int TYPE, class TestFn>
 __device__ __forceinline__ uint32_t scan_type(const VGPU_CONST float* o, float emax, uint32_t acc, TestFn test,
-                                              float x, float y, float z, float r)
+                                              float x, float y, float z, float r, uint32_t skip = 0u)
 {
     // The lane state is kept as VALU bit masks (acc: sign bit = hit) instead of per-lane bools:
     // combining divergent bools costs a 64-bit SALU op each, and the scalar unit -- shared by
@@ -375,7 +414,7 @@ __device__ __forceinline__ uint32_t scan_type(const VGPU_CONST float* o, float e
         // md is sorted: live[u] implies live[0].  ballot of an opaque value: otherwise
         // instcombine folds the test back into an i1 AND, which the backend lowers as
         // compare -> v_cndmask -> compare
-        uint32_t pend = live[0] & ~acc;
+        uint32_t pend = live[0] & ~acc & ~skip;  // skip: all ones for a lane known to be clear (Cleared groups)
         __asm__("" : "+v"(pend));
         if (__builtin_amdgcn_ballot_w64((int)pend < 0) == 0) break;
         float nmd[U];
@@ -388,7 +427,7 @@ __device__ __forceinline__ uint32_t scan_type(const VGPU_CONST float* o, float e
                 const float dx = x - p[u].v[B], dy = y - p[u].v[B + 1], dz = z - p[u].v[B + 2];
                 const float lim = r + p[u].v[B + 3];
                 // NaN distances count as near (the exact test decides them)
-                uint32_t near = (dot3(dx, dy, dz, dx, dy, dz) > lim * lim) ? 0u : live[u] & ~acc;
+                uint32_t near = (dot3(dx, dy, dz, dx, dy, dz) > lim * lim) ? 0u : live[u] & ~acc & ~skip;
                 __asm__("" : "+v"(near));
                 if (__builtin_amdgcn_ballot_w64((int)near < 0) != 0) hit |= __float_as_uint(test(p[u].v)) & live[u];
             } else {
@@ -418,7 +457,7 @@ static_assert(sizeof(SphereBlk) == kSphereBlock * 4, "sphere block layout");
 #define VGPU_SPHERE_PACKED 0
 #endif
 __device__ __forceinline__ uint32_t scan_spheres(const VGPU_CONST float* o, float emax, uint32_t acc, float x, float y,
-                                                 float z, float r)
+                                                 float z, float r, uint32_t skip = 0u)
 {
     const VGPU_CONST SphereBlk* p = (const VGPU_CONST SphereBlk*)o;
     f2v md = p->md;
@@ -426,7 +465,7 @@ __device__ __forceinline__ uint32_t scan_spheres(const VGPU_CONST float* o, floa
         const f2v X = {x, x}, Y = {y, y}, Z = {z, z}, R = {r, r};
         for (;;) {
             const uint32_t la = (md.x < emax) ? 0xFFFFFFFFu : 0u, lb = (md.y < emax) ? 0xFFFFFFFFu : 0u;
-            uint32_t pend = la & ~acc;  // sorted: lb implies la
+            uint32_t pend = la & ~acc & ~skip;  // sorted: lb implies la
             __asm__("" : "+v"(pend));
             if (__builtin_amdgcn_ballot_w64((int)pend < 0) == 0) break;
             const f2v nmd = p[1].md;  // prefetch (sentinel-padded)
@@ -442,7 +481,7 @@ __device__ __forceinline__ uint32_t scan_spheres(const VGPU_CONST float* o, floa
     } else {
         for (;;) {
             const uint32_t la = (md.x < emax) ? 0xFFFFFFFFu : 0u, lb = (md.y < emax) ? 0xFFFFFFFFu : 0u;
-            uint32_t pend = la & ~acc;
+            uint32_t pend = la & ~acc & ~skip;
             __asm__("" : "+v"(pend));
             if (__builtin_amdgcn_ballot_w64((int)pend < 0) == 0) break;
             const f2v nmd = p[1].md;
@@ -724,9 +763,42 @@ __device__ __forceinline__ uint64_t capt_defer_finish(const VGPU_CONST float* pc
 
 template <int TYPE, class TestFn>
 __device__ __forceinline__ uint32_t scan_env_type(const EnvView& env, float emax, uint32_t acc, TestFn test, float x,
-                                                  float y, float z, float r)
+                                                  float y, float z, float r, uint32_t skip = 0u)
 {
-    return scan_type<TYPE>(env.obs[TYPE], emax, acc, test, x, y, z, r);
+    return scan_type<TYPE>(env.obs[TYPE], emax, acc, test, x, y, z, r, skip);
+}
+
+// Clearance lookup (Cleared groups, env.clr_ok): all ones when the environment's grid proves the sphere (x, y, z, r)
+// farther than clr_margin from every obstacle surface, else 0.  No test of a clear sphere can come out negative:
+// every primitive test value is (distance to the record)^2 - r^2 in some form (sphere, capsule, orthonormal
+// cuboid), and the margin (>= 1 mm) is orders of magnitude above the float rounding of those values and above the
+// sub-micron error with which floor((p - lo) * inv_h) may pick a neighbouring cell.  So a clear lane adds no bit
+// to acc whichever records the group's cull admits, and leaving it out of the scans changes nothing.
+// Inside the grid's box: one byte, the cell's lower bound.  Outside: the distance to the AABB of all records.
+// Every comparison is written so that a NaN falls to "scan"; an infinite centre is never clear.
+__device__ __forceinline__ uint32_t clear_lane(const EnvView& env, float x, float y, float z, float r)
+{
+    const float fx = __builtin_floorf((x - env.clr_lo[0]) * env.clr_inv_h[0]);
+    const float fy = __builtin_floorf((y - env.clr_lo[1]) * env.clr_inv_h[1]);
+    const float fz = __builtin_floorf((z - env.clr_lo[2]) * env.clr_inv_h[2]);
+    const float nf = (float)env.clr_n;
+    const bool in = fx >= 0.0f && fx < nf && fy >= 0.0f && fy < nf && fz >= 0.0f && fz < nf;
+    float bound;
+    if (in) {
+        const uint32_t n = (uint32_t)env.clr_n;
+        const uint32_t cell = capt_cell_index((uint32_t)fx, (uint32_t)fy, (uint32_t)fz, n, n, true);
+        bound = (float)env.clr[cell] * kClrStep;  // 0: no statement (r >= 0 is checked below)
+    } else {
+        const float dx = fmaxf(fmaxf(env.clr_a[0] - x, x - env.clr_a[3]), 0.0f);
+        const float dy = fmaxf(fmaxf(env.clr_a[1] - y, y - env.clr_a[4]), 0.0f);
+        const float dz = fmaxf(fmaxf(env.clr_a[2] - z, z - env.clr_a[5]), 0.0f);
+        const float d = __builtin_sqrtf(dot3(dx, dy, dz, dx, dy, dz)) - env.clr_margin;
+        // fmaxf drops a NaN operand: a NaN coordinate is caught by the finiteness test
+        const bool fin = __builtin_fabsf(x) < __builtin_inff() && __builtin_fabsf(y) < __builtin_inff() &&
+                         __builtin_fabsf(z) < __builtin_inff();
+        bound = fin ? d : 0.0f;
+    }
+    return (r >= 0.0f && bound > r) ? 0xFFFFFFFFu : 0u;
 }
 
 // Conservative environment test of a mid-level sphere (tools/gen_kernels.py --mids): sign bit set when the
@@ -739,12 +811,21 @@ template <class Grp>
 __device__ __forceinline__ uint32_t mid_env_bits(const EnvView& env, float x, float y, float z, float r,
                                                  uint32_t acc = 0u)
 {
+    uint32_t skip = 0u;
+    if constexpr (ClearOf<Grp>::on) {
+        if (env.clr_ok) {
+            skip = clear_lane(env, x, y, z, r);
+            uint32_t pend = ~acc & ~skip;
+            __asm__("" : "+v"(pend));
+            if (__builtin_amdgcn_ballot_w64((int)pend < 0) == 0) return acc;  // no lane of the wave left to scan
+        }
+    }
     const float d = dot3(x, y, z, x, y, z);
     float me = (__builtin_sqrtf(d) + r) * 1.001f + 1e-5f;
     if (me != me) me = __builtin_inff();
     const float emax = Grp::max(me);
     const float rsq = r * r;
-    if (env.n[OBS_SPHERE]) acc = scan_spheres(env.obs[OBS_SPHERE], emax, acc, x, y, z, r);
+    if (env.n[OBS_SPHERE]) acc = scan_spheres(env.obs[OBS_SPHERE], emax, acc, x, y, z, r, skip);
     if (env.n[OBS_CAPSULE])
         acc = scan_env_type<OBS_CAPSULE>(env, emax, acc, [&](const auto* o) {
             const float dot = dot3(x - o[1], y - o[2], z - o[3], o[4], o[5], o[6]);
@@ -755,7 +836,7 @@ __device__ __forceinline__ uint32_t mid_env_bits(const EnvView& env, float x, fl
             const float xs = x - px, ys = y - py, zs = z - pz;
             const float rs = r + o[7];
             return __builtin_fmaf(-rs, rs, dot3(xs, ys, zs, xs, ys, zs));
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     if (env.n[OBS_ZCAPSULE])
         acc = scan_env_type<OBS_ZCAPSULE>(env, emax, acc, [&](const auto* o) {
             const float dot = (z - o[3]) * o[6];
@@ -764,7 +845,7 @@ __device__ __forceinline__ uint32_t mid_env_bits(const EnvView& env, float x, fl
             const float xs = x - o[1], ys = y - o[2], zs = z - pz;
             const float rs = r + o[7];
             return __builtin_fmaf(-rs, rs, dot3(xs, ys, zs, xs, ys, zs));
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     if (env.n[OBS_CUBOID])
         acc = scan_env_type<OBS_CUBOID>(env, emax, acc, [&](const auto* o) {
             const float xs = x - o[1], ys = y - o[2], zs = z - o[3];
@@ -772,7 +853,7 @@ __device__ __forceinline__ uint32_t mid_env_bits(const EnvView& env, float x, fl
             const float a2 = max0(__builtin_fabsf(dot3(o[7], o[8], o[9], xs, ys, zs)) - o[14]);
             const float a3 = max0(__builtin_fabsf(dot3(o[10], o[11], o[12], xs, ys, zs)) - o[15]);
             return dot3(a1, a2, a3, a1, a2, a3) - rsq;
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     if (env.n[OBS_ZCUBOID])
         acc = scan_env_type<OBS_ZCUBOID>(env, emax, acc, [&](const auto* o) {
             const float xs = x - o[1], ys = y - o[2], zs = z - o[3];
@@ -780,7 +861,7 @@ __device__ __forceinline__ uint32_t mid_env_bits(const EnvView& env, float x, fl
             const float a2 = max0(__builtin_fabsf(dot2(o[7], o[8], xs, ys)) - o[14]);
             const float a3 = max0(__builtin_fabsf(zs) - o[15]);
             return dot3(a1, a2, a3, a1, a2, a3) - rsq;
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     return acc;
 }
 
@@ -791,6 +872,16 @@ template <class Grp, bool EXT = false>
 __device__ __forceinline__ uint32_t env_bits(const EnvView& env, float x, float y, float z, float r, uint32_t acc = 0u,
                                              int tag = kTagDefault)
 {
+    static_assert(!(EXT && ClearOf<Grp>::on), "the clearance grid covers primitive records only");
+    uint32_t skip = 0u;
+    if constexpr (ClearOf<Grp>::on) {
+        if (env.clr_ok) {
+            skip = clear_lane(env, x, y, z, r);
+            uint32_t pend = ~acc & ~skip;
+            __asm__("" : "+v"(pend));
+            if (__builtin_amdgcn_ballot_w64((int)pend < 0) == 0) return acc;  // no lane of the wave left to scan
+        }
+    }
     const float d = dot3(x, y, z, x, y, z);
     float me = sqrt_host(d, env.lut, env.kbits) + r;  // validity.hh:55-59
     const uint32_t dexp = __float_as_uint(d) & 0x7F800000u;
@@ -798,7 +889,8 @@ __device__ __forceinline__ uint32_t env_bits(const EnvView& env, float x, float 
     const float emax = Grp::max(me);
     const float rsq = r * r;
 
-    if (env.n[OBS_SPHERE]) acc = scan_spheres(env.obs[OBS_SPHERE], emax, acc, x, y, z, r);  // sphere_sphere.hh:10-22
+    if (env.n[OBS_SPHERE])  // sphere_sphere.hh:10-22
+        acc = scan_spheres(env.obs[OBS_SPHERE], emax, acc, x, y, z, r, skip);
     if (env.n[OBS_CAPSULE])  // sphere_capsule.hh:9-22
         acc = scan_env_type<OBS_CAPSULE>(env, emax, acc, [&](const auto* o) {
             const float dot = dot3(x - o[1], y - o[2], z - o[3], o[4], o[5], o[6]);
@@ -809,7 +901,7 @@ __device__ __forceinline__ uint32_t env_bits(const EnvView& env, float x, float 
             const float xs = x - px, ys = y - py, zs = z - pz;
             const float rs = r + o[7];
             return __builtin_fmaf(-rs, rs, dot3(xs, ys, zs, xs, ys, zs));
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     if (env.n[OBS_ZCAPSULE])  // sphere_capsule.hh:30-43
         acc = scan_env_type<OBS_ZCAPSULE>(env, emax, acc, [&](const auto* o) {
             const float dot = (z - o[3]) * o[6];
@@ -818,7 +910,7 @@ __device__ __forceinline__ uint32_t env_bits(const EnvView& env, float x, float 
             const float xs = x - o[1], ys = y - o[2], zs = z - pz;
             const float rs = r + o[7];
             return __builtin_fmaf(-rs, rs, dot3(xs, ys, zs, xs, ys, zs));
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     if (env.n[OBS_CUBOID])  // sphere_cuboid.hh:9-27
         acc = scan_env_type<OBS_CUBOID>(env, emax, acc, [&](const auto* o) {
             const float xs = x - o[1], ys = y - o[2], zs = z - o[3];
@@ -826,7 +918,7 @@ __device__ __forceinline__ uint32_t env_bits(const EnvView& env, float x, float 
             const float a2 = max0(__builtin_fabsf(dot3(o[7], o[8], o[9], xs, ys, zs)) - o[14]);
             const float a3 = max0(__builtin_fabsf(dot3(o[10], o[11], o[12], xs, ys, zs)) - o[15]);
             return dot3(a1, a2, a3, a1, a2, a3) - rsq;
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     if (env.n[OBS_ZCUBOID])  // sphere_cuboid.hh:35-52
         acc = scan_env_type<OBS_ZCUBOID>(env, emax, acc, [&](const auto* o) {
             const float xs = x - o[1], ys = y - o[2], zs = z - o[3];
@@ -834,7 +926,7 @@ __device__ __forceinline__ uint32_t env_bits(const EnvView& env, float x, float 
             const float a2 = max0(__builtin_fabsf(dot2(o[7], o[8], xs, ys)) - o[14]);
             const float a3 = max0(__builtin_fabsf(zs) - o[15]);
             return dot3(a1, a2, a3, a1, a2, a3) - rsq;
-        }, x, y, z, r);
+        }, x, y, z, r, skip);
     if constexpr (EXT) {
         bool hit = (acc >> 31) != 0u;
         for (int i = 0; i < env.n_hf; ++i)

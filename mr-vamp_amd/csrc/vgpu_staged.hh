@@ -256,8 +256,10 @@ struct GrpOf<8> {
 // the group type of a staged kernel: with a point cloud (EXT), undecided CAPT queries are deferred
 // (vgpu_device.hh capt_defer_*) -- in bound kernels under each check's bit (the generated calls pass
 // it), in children kernels under kChildTag
-template <int G, bool EXT, int TAG>
-using StagedGrp = std::conditional_t<EXT, Deferred<typename GrpOf<G>::T, TAG>, typename GrpOf<G>::T>;
+// CLEAR (primitive environments only): the scans consult the environment's clearance grid first (Cleared)
+template <int G, bool EXT, int TAG, bool CLEAR = false>
+using StagedGrp = std::conditional_t<EXT, Deferred<typename GrpOf<G>::T, TAG>,
+                                     std::conditional_t<CLEAR, Cleared<typename GrpOf<G>::T>, typename GrpOf<G>::T>>;
 
 // OR of a 64-bit per-lane mask over the lane's group
 template <class Grp>
@@ -362,6 +364,20 @@ struct MidKinds<R, std::void_t<decltype(R::kMidKinds)>> {
 template <class R, class Src>
 inline constexpr bool kMidBound = ((MidKinds<R>::v >> SrcKindOf<Src>::v) & 1u) != 0u;
 
+// R::kClearKinds (optional, default none): bit k set = the bound kernels of source kind k look every bounding
+// and mid sphere up in the environment's clearance grid before scanning (vgpu_device.hh Cleared, clear_lane).
+// Primitive environments only; results are unchanged.
+template <class R, class = void>
+struct ClearKinds {
+    static constexpr uint32_t v = 0u;
+};
+template <class R>
+struct ClearKinds<R, std::void_t<decltype(R::kClearKinds)>> {
+    static constexpr uint32_t v = R::kClearKinds;
+};
+template <class R, class Src>
+inline constexpr bool kClearBound = ((ClearKinds<R>::v >> SrcKindOf<Src>::v) & 1u) != 0u;
+
 // R::kBothChunks (optional): the bound stage of this pass also computes the NEXT chained pass's masks (the
 // composite's two inter-arm chunks from one FK of both arms, R::bound_both) and stores them after its own,
 // mask[n_groups + g]; the host then skips the next pass's bound kernel and hands it that half
@@ -381,7 +397,7 @@ __global__ __launch_bounds__(kStagedBlock, (BoundWavesE<R, Src, EXT>::v)) void b
                                                                              typename R::Mask* __restrict__ mask,
                                                                              uint8_t* __restrict__ valid)
 {
-    using Grp = StagedGrp<Src::G, EXT, -1>;
+    using Grp = StagedGrp<Src::G, EXT, -1, kClearBound<R, Src>>;
     if constexpr (EXT) {
         capt_stage_lds(env);  // the split tree's top levels into LDS (before any return)
         capt_defer_init();

@@ -33,6 +33,13 @@
 #ifndef VGPU_PANDA_MID_KINDS
 #define VGPU_PANDA_MID_KINDS ((1u << 3) | (1u << 4))
 #endif
+// bound stages that consult the environment's clearance grid (vgpu_staged.hh ClearKinds, bit = SrcKindOf): the
+// validate tails' (3), whose bounding spheres are mostly far from every obstacle: 756 -> 598 us per 2^20 set-B cage
+// edges with 64^3 cells.  Off: the validate heads (2), whose waves are rarely all clear -- the lookups
+// cost more than the skipped trips save (264 -> 275 us, same trace); the full-mask tails (4): no A/B of their own yet.
+#ifndef VGPU_PANDA_CLEAR_KINDS
+#define VGPU_PANDA_CLEAR_KINDS (1u << 3)
+#endif
 #ifndef VGPU_PANDA_LEAD_WAVES
 #define VGPU_PANDA_LEAD_WAVES 8  // 64 VGPRs, no spill (5, the bound stage budget: 67 VGPRs = 7 waves/EU; A/B set B 1.93-1.94 -> 1.90-1.91 ms)
 #endif
@@ -96,6 +103,8 @@ struct PandaR {
     }
     // validate tails (SrcTailT, SrcTailMaskT) run the mid-sphere tests in their bound stage
     static constexpr uint32_t kMidKinds = VGPU_PANDA_MID_KINDS;
+    // validate tails look their bounding and mid spheres up in the clearance grid before scanning
+    static constexpr uint32_t kClearKinds = VGPU_PANDA_CLEAR_KINDS;
     template <class Grp, bool EXT, bool MID = false>
     __device__ static __forceinline__ Mask bound(const float* v, const EnvView& env, const Bases& b)
     {

@@ -300,6 +300,25 @@ class Environment:
         check(load().vgpu_env_upload_stats(self.handle(ctx), out), ctx.h)
         return {"full": int(out[0]), "tail": int(out[1]), "grids": int(out[2])}
 
+    def clear_grid(self, ctx: Optional["Context"] = None):
+        """vgpu_env_clear_grid of the copy on ctx: (header dict, cells) with cells a uint8 array indexed
+        [iz, iy, ix], or (None, None) when the environment has no clearance grid."""
+        ctx = ctx or context()
+        hdr = (C.c_float * 18)()
+        n = C.c_int32()
+        check(load().vgpu_env_clear_grid(self.handle(ctx), hdr, C.byref(n), None, 0), ctx.h)
+        if n.value == 0:
+            return None, None
+        N = int(n.value)
+        raw = np.empty(N * N * N, np.uint8)
+        check(load().vgpu_env_clear_grid(self.handle(ctx), hdr, C.byref(n), raw.ctypes.data, raw.size), ctx.h)
+        h = np.array(hdr[:], np.float32)
+        # storage order: bricks (bz, by, bx) of cells (z, y, x)
+        B = N // 4
+        cells = raw.reshape(B, B, B, 4, 4, 4).transpose(0, 3, 1, 4, 2, 5).reshape(N, N, N)
+        return {"lo": h[0:3], "h": h[3:6], "inv_h": h[6:9], "a_lo": h[9:12], "a_hi": h[12:15], "margin": h[15],
+                "slack": h[16], "step": h[17], "n": N}, cells
+
     @property
     def attached(self) -> bool:
         return any(op[0] == "attach" for op in self._ops)

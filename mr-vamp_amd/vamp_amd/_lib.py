@@ -149,6 +149,7 @@ SIGNATURES = {
     "vgpu_comm_init_loopback": (C.c_int, [VP, C.c_int, VP, C.POINTER(VP)]),
     "vgpu_env_upload_stats": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
     "vgpu_env_pointcloud_grid": (C.c_int, [VP, C.c_int, C.POINTER(C.c_uint32)]),
+    "vgpu_env_clear_grid": (C.c_int, [VP, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t]),
     "vgpu_debug_build": (C.c_int, []),
     "vgpu_debug_violations": (C.c_int, [VP, VP, C.POINTER(C.c_uint32)]),
     "vgpu_ctx_device": (C.c_int, [VP, C.POINTER(C.c_int)]),
