@@ -426,9 +426,29 @@ int vgpu_rrtc_batch_host(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *env, 
                          const float *goals, size_t n_goals, size_t P, const vgpu_rrtc_settings *settings,
                          uint64_t *rng_index, size_t node_cap, float *paths, size_t path_cap, uint32_t *path_len,
                          vgpu_plan_result *results, uint8_t *status);
-/* iterations per problem and launch of the context's later vgpu_rrtc_batch calls (0: the default, 256) */
+/* vgpu_rrtc_batch with one environment per problem: problem p is searched in envs[env_index[p]], and its result
+ * equals vgpu_cpu_rrtc's in that environment bit for bit.  envs[n_envs] (n_envs >= 1) are environments of this
+ * context without an attachment; one may be listed twice, and one that no problem names is allowed.  env_index[P] is
+ * a device pointer: an entry >= n_envs fails the call with VGPU_ERR_INVALID_ARG (the problem does not run, nothing is
+ * read outside the table).  Every environment is uploaded, and the table of their views is copied to a buffer of the
+ * context on its stream, in every call: environments may change between calls.  One launch serves all scenes; it
+ * takes the heightfield / point-cloud kernel if any environment has one, which gives a primitive-only scene the
+ * same results.  Everything else -- buffers, node_cap, path_cap, status, slices -- is vgpu_rrtc_batch's. */
+int vgpu_rrtc_batch_scenes(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *const *envs, size_t n_envs,
+                           const uint32_t *env_index, const float *starts, const float *goals, size_t n_goals,
+                           size_t P, const vgpu_rrtc_settings *settings, uint64_t *rng_index, size_t node_cap,
+                           float *paths, size_t path_cap, uint32_t *path_len, vgpu_plan_result *results,
+                           uint8_t *status);
+/* host pointers (env_index too, checked before anything is launched): copy in, run, copy out, synchronise */
+int vgpu_rrtc_batch_scenes_host(vgpu_ctx *ctx, const vgpu_robot *robot, vgpu_env *const *envs, size_t n_envs,
+                                const uint32_t *env_index, const float *starts, const float *goals, size_t n_goals,
+                                size_t P, const vgpu_rrtc_settings *settings, uint64_t *rng_index, size_t node_cap,
+                                float *paths, size_t path_cap, uint32_t *path_len, vgpu_plan_result *results,
+                                uint8_t *status);
+/* iterations per problem and launch of the context's later vgpu_rrtc_batch / vgpu_rrtc_batch_scenes calls (0: the
+ * default, 256) */
 int vgpu_rrtc_set_slice(vgpu_ctx *ctx, uint32_t slice);
-/* counters of the context's last vgpu_rrtc_batch call: out[0] launches, out[1] iterations summed over the
+/* counters of the context's last vgpu_rrtc_batch / vgpu_rrtc_batch_scenes call: out[0] launches, out[1] iterations summed over the
  * problems, out[2] the largest iteration count of one problem */
 int vgpu_rrtc_stats(const vgpu_ctx *ctx, uint64_t out[3]);
 

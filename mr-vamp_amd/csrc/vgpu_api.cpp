@@ -305,6 +305,10 @@ struct vgpu_ctx {
     unsigned long long* rrtc_host = nullptr;
     uint32_t rrtc_slice = 256;
     uint64_t rrtc_stats[3] = {0, 0, 0};
+    // vgpu_rrtc_batch_scenes: the call's view table on the device and its pinned staging (rrtc_views_cap views each)
+    EnvView* rrtc_views = nullptr;
+    EnvView* rrtc_views_host = nullptr;
+    size_t rrtc_views_cap = 0;
     // roadmap queries (vgpu_roadmap_query.hip): frontier workspace, the pinned round total, the last call's counters
     vgpu::QueryState rq;
     // optional phase timing
@@ -481,6 +485,8 @@ extern "C" void vgpu_ctx_destroy(vgpu_ctx* c)
     if (c->simp_host) (void)hipHostFree(c->simp_host);
     if (c->rrtc) (void)hipFree(c->rrtc);
     if (c->rrtc_host) (void)hipHostFree(c->rrtc_host);
+    if (c->rrtc_views) (void)hipFree(c->rrtc_views);
+    if (c->rrtc_views_host) (void)hipHostFree(c->rrtc_views_host);
     vgpu::query_free(c->rq);
     if (c->tick) (void)hipFree(c->tick);
     if (c->total_host) (void)hipHostFree(c->total_host);
@@ -2835,28 +2841,22 @@ static int rrtc_sizes(vgpu_ctx* c, size_t n_goals, size_t P, size_t node_cap, si
     return VGPU_OK;
 }
 
+// where a call's problems find their environment: one view for all of them (vgpu_rrtc_batch), or the context's
+// device table of n_envs views and an index per problem (vgpu_rrtc_batch_scenes)
+struct RrtcScenes {
+    const EnvView* one = nullptr;
+    const uint32_t* env_index = nullptr;  // device [P]
+    uint32_t n_envs = 0;
+    int ext = 0;  // some environment of the table has a heightfield or a point cloud
+};
+
 // Launches until no problem is working: one slice of every unfinished problem, then ONE synchronisation and
-// read of the pinned totals.  Nothing else crosses to the host while problems run.
-extern "C" int vgpu_rrtc_batch(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, const float* starts, const float* goals,
-                               size_t n_goals, size_t P, const vgpu_rrtc_settings* settings, uint64_t* rng_index,
-                               size_t node_cap, float* paths, size_t path_cap, uint32_t* path_len,
-                               vgpu_plan_result* results, uint8_t* status)
-try {
-    if (!c || !e || e->ctx != c) return fail(c, VGPU_ERR_INVALID_ARG, "bad context/environment");
-    float b[3];
-    int rc = check_robot(c, r, b);
-    if (rc) return rc;
-    if (r->kind != VGPU_ROBOT_PANDA) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch: the Panda only");
-    if (e->attached) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch: no attachments");
-    if (!settings) return fail(c, VGPU_ERR_INVALID_ARG, "null settings");
-    c->rrtc_stats[0] = c->rrtc_stats[1] = c->rrtc_stats[2] = 0;
-    if (P == 0) return VGPU_OK;
-    if ((rc = rrtc_sizes(c, n_goals, P, node_cap, path_cap))) return rc;
-    if (!starts || !goals || !rng_index || !path_len || !results || (path_cap && !paths))
-        return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
-    if ((rc = vgpu_env_upload(e))) return rc;
-    const EnvView v = make_view(e);
-    HIPCHK(c, ctx_device(c));
+// read of the pinned totals.  Nothing else crosses to the host while problems run.  The caller has checked the
+// arguments and uploaded the environments.
+static int rrtc_run(vgpu_ctx* c, const float b[3], const RrtcScenes& sc, const float* starts, const float* goals,
+                    size_t n_goals, size_t P, const vgpu_rrtc_settings* settings, uint64_t* rng_index, size_t node_cap,
+                    float* paths, size_t path_cap, uint32_t* path_len, vgpu_plan_result* results, uint8_t* status)
+{
     const size_t slots = P * node_cap;
     const size_t nb = al(slots * 7 * 4), pb = al(slots * 4), tb = al(slots), cb = al(P * vgpu::kRrtcWords * 4);
     const size_t need = nb + 2 * pb + tb + cb + 256;
@@ -2871,7 +2871,7 @@ try {
         c->rrtc_bytes = need;
     }
     if (!c->rrtc_host)
-        HIPCHK(c, hipHostMalloc((void**)&c->rrtc_host, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIPCHK(c, hipHostMalloc((void**)&c->rrtc_host, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     char* p = (char*)c->rrtc;
     vgpu::RrtcArgs a{};
     a.starts = starts;
@@ -2908,15 +2908,105 @@ try {
     a.bz = b[2];
     HIPCHK(c, hipMemsetAsync(a.ctl, 0, cb + 256, c->cur));  // every problem RPH_NEW, the totals zero
     for (;;) {
-        HIPCHK(c, vgpu_launch_rrtc(&a, &v, totals, c->rrtc_host, c->cur));
+        if (sc.one)
+            HIPCHK(c, vgpu_launch_rrtc(&a, sc.one, totals, c->rrtc_host, c->cur));
+        else
+            HIPCHK(c, vgpu_launch_rrtc_scenes(&a, c->rrtc_views, sc.env_index, sc.n_envs, sc.ext, totals, c->rrtc_host,
+                                              c->cur));
         HIPCHK(c, hipStreamSynchronize(c->cur));
         if (c->rrtc_host[3]) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: rng_index entries must be at least 1");
+        if (c->rrtc_host[4]) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: env_index entries must be below n_envs");
         c->rrtc_stats[0] += 1;
         c->rrtc_stats[1] = c->rrtc_host[1];
         c->rrtc_stats[2] = c->rrtc_host[2];
         if (!c->rrtc_host[0]) break;
     }
     return VGPU_OK;
+}
+
+extern "C" int vgpu_rrtc_batch(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, const float* starts, const float* goals,
+                               size_t n_goals, size_t P, const vgpu_rrtc_settings* settings, uint64_t* rng_index,
+                               size_t node_cap, float* paths, size_t path_cap, uint32_t* path_len,
+                               vgpu_plan_result* results, uint8_t* status)
+try {
+    if (!c || !e || e->ctx != c) return fail(c, VGPU_ERR_INVALID_ARG, "bad context/environment");
+    float b[3];
+    int rc = check_robot(c, r, b);
+    if (rc) return rc;
+    if (r->kind != VGPU_ROBOT_PANDA) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch: the Panda only");
+    if (e->attached) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch: no attachments");
+    if (!settings) return fail(c, VGPU_ERR_INVALID_ARG, "null settings");
+    c->rrtc_stats[0] = c->rrtc_stats[1] = c->rrtc_stats[2] = 0;
+    if (P == 0) return VGPU_OK;
+    if ((rc = rrtc_sizes(c, n_goals, P, node_cap, path_cap))) return rc;
+    if (!starts || !goals || !rng_index || !path_len || !results || (path_cap && !paths))
+        return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    if ((rc = vgpu_env_upload(e))) return rc;
+    const EnvView v = make_view(e);
+    HIPCHK(c, ctx_device(c));
+    RrtcScenes sc;
+    sc.one = &v;
+    return rrtc_run(c, b, sc, starts, goals, n_goals, P, settings, rng_index, node_cap, paths, path_cap, path_len, results,
+                    status);
+} VGPU_ABI_CATCH
+
+// the environments of a multi-scene call, checked by vgpu_rrtc_batch's rules
+static int rrtc_check_envs(vgpu_ctx* c, vgpu_env* const* envs, size_t n_envs)
+{
+    if (!envs || n_envs == 0) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc_batch_scenes: at least one environment");
+    if (n_envs >= ((size_t)1 << 31)) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc_batch_scenes: n_envs must be below 2^31");
+    for (size_t i = 0; i < n_envs; ++i)
+        if (!envs[i] || envs[i]->ctx != c) return fail(c, VGPU_ERR_INVALID_ARG, "bad context/environment");
+    return VGPU_OK;
+}
+
+extern "C" int vgpu_rrtc_batch_scenes(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* const* envs, size_t n_envs,
+                                      const uint32_t* env_index, const float* starts, const float* goals, size_t n_goals,
+                                      size_t P, const vgpu_rrtc_settings* settings, uint64_t* rng_index, size_t node_cap,
+                                      float* paths, size_t path_cap, uint32_t* path_len, vgpu_plan_result* results,
+                                      uint8_t* status)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    int rc = rrtc_check_envs(c, envs, n_envs);
+    if (rc) return rc;
+    float b[3];
+    if ((rc = check_robot(c, r, b))) return rc;
+    if (r->kind != VGPU_ROBOT_PANDA) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch_scenes: the Panda only");
+    for (size_t i = 0; i < n_envs; ++i)
+        if (envs[i]->attached) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch_scenes: no attachments");
+    if (!settings) return fail(c, VGPU_ERR_INVALID_ARG, "null settings");
+    c->rrtc_stats[0] = c->rrtc_stats[1] = c->rrtc_stats[2] = 0;
+    if (P == 0) return VGPU_OK;
+    if ((rc = rrtc_sizes(c, n_goals, P, node_cap, path_cap))) return rc;
+    if (!env_index || !starts || !goals || !rng_index || !path_len || !results || (path_cap && !paths))
+        return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    for (size_t i = 0; i < n_envs; ++i)
+        if ((rc = vgpu_env_upload(envs[i]))) return rc;
+    HIPCHK(c, ctx_device(c));
+    if (n_envs > c->rrtc_views_cap) {
+        // an earlier call's copy out of the staging has completed: every call ends behind a synchronisation
+        HIPCHK(c, hipStreamSynchronize(c->cur));
+        if (c->rrtc_views) HIPCHK(c, hipFree(c->rrtc_views));
+        if (c->rrtc_views_host) HIPCHK(c, hipHostFree(c->rrtc_views_host));
+        c->rrtc_views = c->rrtc_views_host = nullptr;
+        c->rrtc_views_cap = 0;
+        const size_t cap = std::max<size_t>(16, n_envs + n_envs / 2);
+        HIPCHK(c, hipMalloc((void**)&c->rrtc_views, cap * sizeof(EnvView)));
+        HIPCHK(c, hipHostMalloc((void**)&c->rrtc_views_host, cap * sizeof(EnvView), hipHostMallocDefault));
+        c->rrtc_views_cap = cap;
+    }
+    // the table of THIS call (environments may have changed since the last one).  The pinned staging is read by the
+    // copy before the first launch's synchronisation below and not written again before the next call.
+    RrtcScenes sc;
+    for (size_t i = 0; i < n_envs; ++i) {
+        c->rrtc_views_host[i] = make_view(envs[i]);
+        if (c->rrtc_views_host[i].n_hf > 0 || c->rrtc_views_host[i].n_pc > 0) sc.ext = 1;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->rrtc_views, c->rrtc_views_host, n_envs * sizeof(EnvView), hipMemcpyHostToDevice, c->cur));
+    sc.env_index = env_index;
+    sc.n_envs = (uint32_t)n_envs;
+    return rrtc_run(c, b, sc, starts, goals, n_goals, P, settings, rng_index, node_cap, paths, path_cap, path_len, results,
+                    status);
 } VGPU_ABI_CATCH
 
 extern "C" int vgpu_rrtc_set_slice(vgpu_ctx* c, uint32_t slice)
@@ -2933,6 +3023,48 @@ try {
     return VGPU_OK;
 } VGPU_ABI_CATCH
 
+// host pointers, after the caller's checks: copy in, run (in e, or in envs[env_index[p]] when envs is given), copy
+// out, synchronise
+static int rrtc_host_run(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, vgpu_env* const* envs, size_t n_envs,
+                         const uint32_t* env_index, const float* starts, const float* goals, size_t n_goals, size_t P,
+                         const vgpu_rrtc_settings* settings, uint64_t* rng_index, size_t node_cap, float* paths,
+                         size_t path_cap, uint32_t* path_len, vgpu_plan_result* results, uint8_t* status)
+{
+    int rc;
+    char* d;
+    const size_t dim = dim_of(r);
+    const size_t sbytes = P * dim * 4, gbytes = P * n_goals * dim * 4, wbytes = P * path_cap * dim * 4;
+    const size_t sb = al(sbytes), gb = al(gbytes), ib = al(P * 8), wb = al(wbytes), lb = al(P * 4),
+                 rb = al(P * sizeof(vgpu_plan_result));
+    if ((rc = stage(c, sb + gb + ib + wb + lb + rb + al(P) + (envs ? al(P * 4) : 0), &d))) return rc;
+    float* sd = (float*)d;
+    float* gd = (float*)(d + sb);
+    uint64_t* id = (uint64_t*)(d + sb + gb);
+    float* wd = (float*)(d + sb + gb + ib);
+    uint32_t* ld = (uint32_t*)(d + sb + gb + ib + wb);
+    vgpu_plan_result* rd = (vgpu_plan_result*)(d + sb + gb + ib + wb + lb);
+    uint8_t* std_ = (uint8_t*)(d + sb + gb + ib + wb + lb + rb);
+    HIPCHK(c, hipMemcpyAsync(sd, starts, sbytes, hipMemcpyHostToDevice, c->cur));
+    HIPCHK(c, hipMemcpyAsync(gd, goals, gbytes, hipMemcpyHostToDevice, c->cur));
+    HIPCHK(c, hipMemcpyAsync(id, rng_index, P * 8, hipMemcpyHostToDevice, c->cur));
+    if (envs) {
+        uint32_t* ed = (uint32_t*)(d + sb + gb + ib + wb + lb + rb + al(P));
+        HIPCHK(c, hipMemcpyAsync(ed, env_index, P * 4, hipMemcpyHostToDevice, c->cur));
+        rc = vgpu_rrtc_batch_scenes(c, r, envs, n_envs, ed, sd, gd, n_goals, P, settings, id, node_cap, wd, path_cap, ld,
+                                    rd, std_);
+    } else {
+        rc = vgpu_rrtc_batch(c, r, e, sd, gd, n_goals, P, settings, id, node_cap, wd, path_cap, ld, rd, std_);
+    }
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(rng_index, id, P * 8, hipMemcpyDeviceToHost, c->cur));
+    if (wbytes) HIPCHK(c, hipMemcpyAsync(paths, wd, wbytes, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipMemcpyAsync(path_len, ld, P * 4, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipMemcpyAsync(results, rd, P * sizeof(vgpu_plan_result), hipMemcpyDeviceToHost, c->cur));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, std_, P, hipMemcpyDeviceToHost, c->cur));
+    HIPCHK(c, hipStreamSynchronize(c->cur));
+    return VGPU_OK;
+}
+
 extern "C" int vgpu_rrtc_batch_host(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* e, const float* starts,
                                     const float* goals, size_t n_goals, size_t P, const vgpu_rrtc_settings* settings,
                                     uint64_t* rng_index, size_t node_cap, float* paths, size_t path_cap,
@@ -2947,31 +3079,35 @@ try {
     if ((rc = rrtc_sizes(c, n_goals, P, node_cap, path_cap))) return rc;
     if (!starts || !goals || !rng_index || !path_len || !results || (path_cap && !paths))
         return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
-    char* d;
-    const size_t dim = dim_of(r);
-    const size_t sbytes = P * dim * 4, gbytes = P * n_goals * dim * 4, wbytes = P * path_cap * dim * 4;
-    const size_t sb = al(sbytes), gb = al(gbytes), ib = al(P * 8), wb = al(wbytes), lb = al(P * 4),
-                 rb = al(P * sizeof(vgpu_plan_result));
-    if ((rc = stage(c, sb + gb + ib + wb + lb + rb + al(P), &d))) return rc;
-    float* sd = (float*)d;
-    float* gd = (float*)(d + sb);
-    uint64_t* id = (uint64_t*)(d + sb + gb);
-    float* wd = (float*)(d + sb + gb + ib);
-    uint32_t* ld = (uint32_t*)(d + sb + gb + ib + wb);
-    vgpu_plan_result* rd = (vgpu_plan_result*)(d + sb + gb + ib + wb + lb);
-    uint8_t* std_ = (uint8_t*)(d + sb + gb + ib + wb + lb + rb);
-    HIPCHK(c, hipMemcpyAsync(sd, starts, sbytes, hipMemcpyHostToDevice, c->cur));
-    HIPCHK(c, hipMemcpyAsync(gd, goals, gbytes, hipMemcpyHostToDevice, c->cur));
-    HIPCHK(c, hipMemcpyAsync(id, rng_index, P * 8, hipMemcpyHostToDevice, c->cur));
-    if ((rc = vgpu_rrtc_batch(c, r, e, sd, gd, n_goals, P, settings, id, node_cap, wd, path_cap, ld, rd, std_)))
-        return rc;
-    HIPCHK(c, hipMemcpyAsync(rng_index, id, P * 8, hipMemcpyDeviceToHost, c->cur));
-    if (wbytes) HIPCHK(c, hipMemcpyAsync(paths, wd, wbytes, hipMemcpyDeviceToHost, c->cur));
-    HIPCHK(c, hipMemcpyAsync(path_len, ld, P * 4, hipMemcpyDeviceToHost, c->cur));
-    HIPCHK(c, hipMemcpyAsync(results, rd, P * sizeof(vgpu_plan_result), hipMemcpyDeviceToHost, c->cur));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, std_, P, hipMemcpyDeviceToHost, c->cur));
-    HIPCHK(c, hipStreamSynchronize(c->cur));
-    return VGPU_OK;
+    return rrtc_host_run(c, r, e, nullptr, 0, nullptr, starts, goals, n_goals, P, settings, rng_index, node_cap, paths,
+                         path_cap, path_len, results, status);
+} VGPU_ABI_CATCH
+
+// env_index is checked here, before anything is copied or launched
+extern "C" int vgpu_rrtc_batch_scenes_host(vgpu_ctx* c, const vgpu_robot* r, vgpu_env* const* envs, size_t n_envs,
+                                           const uint32_t* env_index, const float* starts, const float* goals,
+                                           size_t n_goals, size_t P, const vgpu_rrtc_settings* settings,
+                                           uint64_t* rng_index, size_t node_cap, float* paths, size_t path_cap,
+                                           uint32_t* path_len, vgpu_plan_result* results, uint8_t* status)
+try {
+    if (!c) return VGPU_ERR_INVALID_ARG;
+    int rc = rrtc_check_envs(c, envs, n_envs);
+    if (rc) return rc;
+    float b[3];
+    if ((rc = check_robot(c, r, b))) return rc;
+    if (r->kind != VGPU_ROBOT_PANDA) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch_scenes: the Panda only");
+    for (size_t i = 0; i < n_envs; ++i)
+        if (envs[i]->attached) return fail(c, VGPU_ERR_UNSUPPORTED, "rrtc_batch_scenes: no attachments");
+    if (!settings) return fail(c, VGPU_ERR_INVALID_ARG, "null settings");
+    c->rrtc_stats[0] = c->rrtc_stats[1] = c->rrtc_stats[2] = 0;
+    if (P == 0) return VGPU_OK;
+    if ((rc = rrtc_sizes(c, n_goals, P, node_cap, path_cap))) return rc;
+    if (!env_index || !starts || !goals || !rng_index || !path_len || !results || (path_cap && !paths))
+        return fail(c, VGPU_ERR_INVALID_ARG, "null buffers");
+    for (size_t p = 0; p < P; ++p)
+        if (env_index[p] >= n_envs) return fail(c, VGPU_ERR_INVALID_ARG, "rrtc: env_index entries must be below n_envs");
+    return rrtc_host_run(c, r, nullptr, envs, n_envs, env_index, starts, goals, n_goals, P, settings, rng_index, node_cap,
+                         paths, path_cap, path_len, results, status);
 } VGPU_ABI_CATCH
 
 // ---- roadmap queries (planning/prm.hh:168-187; kernels and round loops in vgpu_roadmap_query.hip) --------------

@@ -1,5 +1,5 @@
-// vgpu_rrtc.hh -- arguments of the batched RRT-Connect kernel (vgpu_rrtc.hip), shared with the driver in
-// vgpu_api.cpp.
+// vgpu_rrtc.hh -- arguments of the batched RRT-Connect kernels (vgpu_rrtc.hip: one environment per call, or one per
+// problem), shared with the driver in vgpu_api.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,10 +52,16 @@ struct RrtcArgs {
 }  // namespace vgpu
 
 extern "C" {
-// totals[4] (device, zero before the first launch, as the control words: RPH_NEW = 0): [0] problems the last
+// totals[5] (device, zero before the first launch, as the control words: RPH_NEW = 0): [0] problems the last
 // launch left unfinished, [1] iterations summed over the finished problems, [2] the largest iteration count of
-// one problem, [3] problems whose rng entry is 0 (the argument check; they do not run).
-// one slice of every unfinished problem; then totals -> host_totals[4] (pinned) and totals[0] = 0
+// one problem, [3] problems whose rng entry is 0 (the argument check; they do not run), [4] problems whose
+// env_index entry is outside the view table (likewise; vgpu_launch_rrtc_scenes only).
+// one slice of every unfinished problem; then totals -> host_totals[5] (pinned) and totals[0] = 0
 hipError_t vgpu_launch_rrtc(const vgpu::RrtcArgs* a, const EnvView* env, unsigned long long* totals,
                             unsigned long long* host_totals, hipStream_t st);
+// the same with one environment per problem: problem p searches in views[env_index[p]] (views: a device table of
+// n_envs views, env_index: device [P]); ext: some view has a heightfield or a point cloud
+hipError_t vgpu_launch_rrtc_scenes(const vgpu::RrtcArgs* a, const EnvView* views, const uint32_t* env_index,
+                                   uint32_t n_envs, int ext, unsigned long long* totals,
+                                   unsigned long long* host_totals, hipStream_t st);
 }

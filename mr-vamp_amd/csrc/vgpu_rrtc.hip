@@ -1,9 +1,11 @@
 // vgpu_rrtc.hip -- batched RRT-Connect (planning/rrtc.hh:33-248): one wave per planning problem.
 //
-// P problems in one environment each follow vcpu_rrtc.cpp statement for statement; nothing couples them, so a
-// problem is one wave64 that runs its whole search inside the kernel -- sampling, nearest neighbours, the
-// inline collision check, tree growth and path extraction -- and the host only relaunches until no problem is
-// left working (a launch advances a problem by at most `slice` iterations, so every launch is short).
+// P problems each follow vcpu_rrtc.cpp statement for statement, all in one environment (rrtc_kernel) or each in the
+// environment it names (rrtc_scenes_kernel: a device table of views and an index per problem; the search itself,
+// rrtc_search, is the same function).  Nothing couples them, so a problem is one wave64 that runs its whole
+// search inside the kernel -- sampling, nearest neighbours, the inline collision check, tree growth and path
+// extraction -- and the host only relaunches until no problem is left working (a launch advances a problem by at
+// most `slice` iterations, so every launch is short).
 //   state      wave-uniform values in registers; the trees in the problem's arena (nodes in insertion order
 //              with parent, dynamic-domain radius and tree membership), the control words of vgpu_rrtc.hh
 //              between launches;
@@ -17,8 +19,8 @@
 //              free: in the connect phase they take the next segments (start = prior + inc iterated), and the
 //              first failing segment in order ends the connect.  Validity is the AND of a segment's blocks, so
 //              the blocks evaluated beyond the CPU's sequential early exit cannot change it.
-// There is ONE panda_fkcc call site: the loop below is a state machine around it (M_*), because the generated
-// function is thousands of instructions and is inlined.
+// There is ONE panda_fkcc call site per kernel: the loop below is a state machine around it (M_*), because the
+// generated function is thousands of instructions and is inlined.
 // Arithmetic is the CPU's, bit for bit (-ffp-contract=off, IEEE division and sqrt).
 #include <hip/hip_runtime.h>
 
@@ -126,14 +128,13 @@ __device__ __forceinline__ uint32_t nearest(const Arena& t, uint32_t n_nodes, ui
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)bi);
 }
 
+// one slice of problem p's search in `env` (wave-uniform): the body of both entry kernels below, which differ only
+// in where the view comes from.  phase != RPH_DONE (the kernels return before they read a view).
 template <bool EXT>
-__global__ __launch_bounds__(kWave) void rrtc_kernel(RrtcArgs a, EnvView env, unsigned long long* __restrict__ totals)
+__device__ __forceinline__ void rrtc_search(const RrtcArgs& a, const EnvView& env, unsigned long long* __restrict__ totals,
+                                            uint32_t p, uint32_t* ctl, uint32_t phase)
 {
-    const uint32_t p = blockIdx.x;
     const int lane = (int)threadIdx.x, g = lane >> 3, gl = lane & 7;
-    uint32_t* ctl = a.ctl + (size_t)p * kRrtcWords;
-    const uint32_t phase = ctl[RC_PHASE];
-    if (phase == RPH_DONE) return;  // wave-uniform
 
     Arena t;
     t.nodes = a.nodes + (size_t)p * a.node_cap * 7;
@@ -462,6 +463,49 @@ __global__ __launch_bounds__(kWave) void rrtc_kernel(RrtcArgs a, EnvView env, un
     atomicMax(totals + 2, (unsigned long long)iter);
 }
 
+// one environment for every problem: the view is a kernel argument
+template <bool EXT>
+__global__ __launch_bounds__(kWave) void rrtc_kernel(RrtcArgs a, EnvView env, unsigned long long* __restrict__ totals)
+{
+    const uint32_t p = blockIdx.x;
+    uint32_t* ctl = a.ctl + (size_t)p * kRrtcWords;
+    const uint32_t phase = ctl[RC_PHASE];
+    if (phase == RPH_DONE) return;  // wave-uniform
+    rrtc_search<EXT>(a, env, totals, p, ctl, phase);
+}
+
+// one environment per problem: wave p searches in views[env_index[p]].  The index is read through readfirstlane and
+// the table lies in the constant address space, so the view's fields arrive by scalar loads into SGPRs, as the
+// kernel argument's do.  An index outside the table ends the problem unrun and counts in totals[4] (the host fails
+// the call), the pattern of rng == 0 on totals[3]: no view is read for it.
+template <bool EXT>
+__global__ __launch_bounds__(kWave) void rrtc_scenes_kernel(RrtcArgs a, const VGPU_CONST EnvView* __restrict__ views,
+                                                            const uint32_t* __restrict__ env_index, uint32_t n_envs,
+                                                            unsigned long long* __restrict__ totals)
+{
+    const uint32_t p = blockIdx.x;
+    uint32_t* ctl = a.ctl + (size_t)p * kRrtcWords;
+    const uint32_t phase = ctl[RC_PHASE];
+    if (phase == RPH_DONE) return;  // wave-uniform
+    const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)env_index[p]);
+    if (e >= n_envs) {
+        if (threadIdx.x == 0) {
+            ctl[RC_PHASE] = RPH_DONE;
+            atomicAdd(totals + 4, 1ull);
+        }
+        return;
+    }
+    static_assert(sizeof(EnvView) % 4 == 0 && alignof(EnvView) >= 4, "the view is copied word by word");
+    union {
+        EnvView v;
+        uint32_t w[sizeof(EnvView) / 4];
+    } env;
+    const VGPU_CONST uint32_t* src = (const VGPU_CONST uint32_t*)(views + e);
+#pragma unroll
+    for (size_t i = 0; i < sizeof(EnvView) / 4; ++i) env.w[i] = src[i];
+    rrtc_search<EXT>(a, env.v, totals, p, ctl, phase);
+}
+
 // the launch's counters to the pinned words the host reads after its synchronisation
 __global__ void rrtc_report_kernel(unsigned long long* __restrict__ totals, unsigned long long* __restrict__ host)
 {
@@ -469,6 +513,7 @@ __global__ void rrtc_report_kernel(unsigned long long* __restrict__ totals, unsi
     host[1] = totals[1];
     host[2] = totals[2];
     host[3] = totals[3];
+    host[4] = totals[4];
     totals[0] = 0;
 }
 
@@ -481,6 +526,23 @@ extern "C" hipError_t vgpu_launch_rrtc(const vgpu::RrtcArgs* a, const EnvView* e
         hipLaunchKernelGGL(vgpu::rrtc_kernel<true>, dim3(a->P), dim3(vgpu::kWave), 0, st, *a, *env, totals);
     else
         hipLaunchKernelGGL(vgpu::rrtc_kernel<false>, dim3(a->P), dim3(vgpu::kWave), 0, st, *a, *env, totals);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(vgpu::rrtc_report_kernel, dim3(1), dim3(1), 0, st, totals, host_totals);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t vgpu_launch_rrtc_scenes(const vgpu::RrtcArgs* a, const EnvView* views, const uint32_t* env_index,
+                                              uint32_t n_envs, int ext, unsigned long long* totals,
+                                              unsigned long long* host_totals, hipStream_t st)
+{
+    const VGPU_CONST EnvView* v = (const VGPU_CONST EnvView*)views;
+    if (ext)
+        hipLaunchKernelGGL(vgpu::rrtc_scenes_kernel<true>, dim3(a->P), dim3(vgpu::kWave), 0, st, *a, v, env_index, n_envs,
+                           totals);
+    else
+        hipLaunchKernelGGL(vgpu::rrtc_scenes_kernel<false>, dim3(a->P), dim3(vgpu::kWave), 0, st, *a, v, env_index, n_envs,
+                           totals);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(vgpu::rrtc_report_kernel, dim3(1), dim3(1), 0, st, totals, host_totals);

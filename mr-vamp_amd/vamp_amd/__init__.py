@@ -925,7 +925,7 @@ class Robot:
         check(load().vgpu_simplify_stats(ctx.h, s), ctx.h)
         return {"rounds": int(s[0]), "validate_calls": int(s[1]), "edges": int(s[2])}
 
-    # per-problem outcome of rrtc_batch / rrtc_device (VGPU_RRTC_*)
+    # per-problem outcome of rrtc_batch / rrtc_batch_scenes and their device forms (VGPU_RRTC_*)
     RRTC_DONE, RRTC_CAPACITY, RRTC_PATH_CAPACITY = 0, 1, 2
 
     def rrtc_batch(self, starts, goals, environment: Environment, settings: Optional[RRTCSettings] = None,
@@ -965,17 +965,21 @@ class Robot:
         finally:
             if slice is not None:
                 load().vgpu_rrtc_set_slice(ctx.h, 0)
-        # the records as arrays: one pass over a structured view instead of ctypes field reads per problem
+        return self._rrtc_results(res, paths, ln, st), st, idx
+
+    def _rrtc_results(self, res, paths, ln, st):
+        """[PlanningResult] of a batch's records: one pass over a structured view instead of ctypes field reads
+        per problem"""
         rec = np.frombuffer(res, dtype=_PLAN_RESULT_DTYPE)
         solved, its, cost = rec["solved"].tolist(), rec["iterations"].tolist(), rec["cost"].tolist()
         sizes, lens, stl = rec["size"].tolist(), ln.tolist(), st.tolist()
         out = []
-        for i in range(n):
+        for i in range(len(lens)):
             kept = lens[i] if stl[i] != self.RRTC_PATH_CAPACITY else 0
             pr = PlanningResult(paths[i, :kept].copy(), cost[i], its[i], (sizes[i][0], sizes[i][1]), 0, bool(solved[i]))
             pr.status, pr.path_len = stl[i], lens[i]
             out.append(pr)
-        return out, st, idx
+        return out
 
     def rrtc_device(self, starts_ptr: int, goals_ptr: int, n_goals: int, n_problems: int, environment: Environment,
                     settings: Optional[RRTCSettings], rng_index_ptr: int, node_cap: int, paths_ptr: int, path_cap: int,
@@ -991,8 +995,77 @@ class Robot:
                                      C.c_void_p(path_len_ptr), C.c_void_p(results_ptr), C.c_void_p(status_ptr or 0)),
               ctx.h)
 
+    def rrtc_batch_scenes(self, starts, goals, environments: Sequence[Environment], env_index=None,
+                          settings: Optional[RRTCSettings] = None, rng_first=1, node_cap: int = 4096,
+                          path_cap: int = 256, ctx: Optional[Context] = None, slice: Optional[int] = None):
+        """rrtc_batch() with one environment per problem, still one call and one wave per problem
+        (vgpu_rrtc_batch_scenes_host): problem p is planned in environments[env_index[p]], and its result equals
+        rrtc()'s in that environment bit for bit.  env_index defaults to 0 .. P - 1 when there are as many
+        environments as problems and is required otherwise; an environment may be listed twice, shared by several
+        problems, or named by none.  Everything else, and the returned triple, is rrtc_batch()'s."""
+        dim = self.dimension()
+        s = np.ascontiguousarray(starts, np.float32).reshape(-1, dim)
+        n = s.shape[0]
+        environments = list(environments)
+        if env_index is None:
+            if len(environments) != n:
+                raise ValueError(f"env_index is required: {len(environments)} environments for {n} problems")
+            ei = np.arange(n, dtype=np.uint32)
+        else:
+            ei = np.asarray(env_index)
+            if ei.shape != (n,):
+                raise ValueError(f"env_index must have one entry per problem ({n}), got shape {ei.shape}")
+            if n and (ei.min() < 0 or ei.max() > 0xFFFFFFFF):
+                raise ValueError("env_index entries must be unsigned 32-bit indices")
+            ei = np.ascontiguousarray(ei, np.uint32)
+        ctx = ctx or context()
+        settings = settings or RRTCSettings()
+        envs = (C.c_void_p * max(len(environments), 1))(*[e.handle(ctx) for e in environments])
+        g = np.ascontiguousarray(goals, np.float32).reshape(n, -1, dim) if n else np.zeros((0, 1, dim), np.float32)
+        idx = np.array(np.broadcast_to(np.asarray(rng_first, np.uint64), (n,)))  # a copy: advanced in place
+        node_cap, path_cap = int(node_cap), int(path_cap)
+        paths = np.zeros((n, path_cap, dim), np.float32)
+        ln = np.zeros(n, np.uint32)
+        res = (_lib.VgpuPlanResult * max(n, 1))()
+        st = np.zeros(n, np.uint8)
+        cs = settings.c()
+        if slice is not None:
+            check(load().vgpu_rrtc_set_slice(ctx.h, int(slice)), ctx.h)
+        try:
+            check(load().vgpu_rrtc_batch_scenes_host(ctx.h, C.byref(self.c_robot), envs, len(environments),
+                                                     ei.ctypes.data_as(_lib.U32P), s.ctypes.data_as(_lib.F32P),
+                                                     g.ctypes.data_as(_lib.F32P), g.shape[1], n, C.byref(cs),
+                                                     idx.ctypes.data_as(_lib.U64P), node_cap,
+                                                     paths.ctypes.data_as(_lib.F32P), path_cap,
+                                                     ln.ctypes.data_as(_lib.U32P), res, st.ctypes.data_as(_lib.U8P)),
+                  ctx.h)
+        finally:
+            if slice is not None:
+                load().vgpu_rrtc_set_slice(ctx.h, 0)
+        if n == 0:
+            return [], st, idx
+        return self._rrtc_results(res, paths, ln, st), st, idx
+
+    def rrtc_scenes_device(self, starts_ptr: int, goals_ptr: int, n_goals: int, n_problems: int,
+                           environments: Sequence[Environment], env_index_ptr: int, settings: Optional[RRTCSettings],
+                           rng_index_ptr: int, node_cap: int, paths_ptr: int, path_cap: int, path_len_ptr: int,
+                           results_ptr: int, status_ptr: int = 0, ctx: Optional[Context] = None):
+        """vgpu_rrtc_batch_scenes over device memory: rrtc_device() with environments and env_index uint32 [P] on
+        the device (an entry outside the list fails the call).  Problems sorted by scene leave each scene's paths
+        a contiguous sub-range of paths / path_len, which simplify_device takes with offset pointers."""
+        ctx = ctx or context()
+        cs = (settings or RRTCSettings()).c()
+        environments = list(environments)
+        envs = (C.c_void_p * max(len(environments), 1))(*[e.handle(ctx) for e in environments])
+        check(load().vgpu_rrtc_batch_scenes(ctx.h, C.byref(self.c_robot), envs, len(environments),
+                                            C.c_void_p(env_index_ptr), C.c_void_p(starts_ptr), C.c_void_p(goals_ptr),
+                                            int(n_goals), int(n_problems), C.byref(cs), C.c_void_p(rng_index_ptr),
+                                            int(node_cap), C.c_void_p(paths_ptr), int(path_cap),
+                                            C.c_void_p(path_len_ptr), C.c_void_p(results_ptr),
+                                            C.c_void_p(status_ptr or 0)), ctx.h)
+
     def rrtc_stats(self, ctx: Optional[Context] = None) -> dict:
-        """counters of the context's last rrtc_batch / rrtc_device call"""
+        """counters of the context's last rrtc_batch / rrtc_batch_scenes / rrtc_device / rrtc_scenes_device call"""
         ctx = ctx or context()
         s = (C.c_uint64 * 3)()
         check(load().vgpu_rrtc_stats(ctx.h, s), ctx.h)

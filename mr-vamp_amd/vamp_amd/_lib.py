@@ -179,6 +179,12 @@ SIGNATURES = {
     "vgpu_rrtc_batch_host": (C.c_int, [VP, C.POINTER(VgpuRobot), VP, F32P, F32P, C.c_size_t, C.c_size_t,
                                        C.POINTER(VgpuRrtcSettings), U64P, C.c_size_t, F32P, C.c_size_t, U32P,
                                        C.POINTER(VgpuPlanResult), U8P]),
+    "vgpu_rrtc_batch_scenes": (C.c_int, [VP, C.POINTER(VgpuRobot), C.POINTER(VP), C.c_size_t, VP, VP, VP, C.c_size_t,
+                                         C.c_size_t, C.POINTER(VgpuRrtcSettings), VP, C.c_size_t, VP, C.c_size_t, VP, VP,
+                                         VP]),
+    "vgpu_rrtc_batch_scenes_host": (C.c_int, [VP, C.POINTER(VgpuRobot), C.POINTER(VP), C.c_size_t, U32P, F32P, F32P,
+                                              C.c_size_t, C.c_size_t, C.POINTER(VgpuRrtcSettings), U64P, C.c_size_t,
+                                              F32P, C.c_size_t, U32P, C.POINTER(VgpuPlanResult), U8P]),
     "vgpu_rrtc_set_slice": (C.c_int, [VP, C.c_uint32]),
     "vgpu_rrtc_stats": (C.c_int, [VP, C.POINTER(C.c_uint64)]),
     "vgpu_build_roadmap_host": (C.c_int, [VP, C.POINTER(VgpuRobot), VP, F32P, C.c_size_t, C.c_double, C.c_double,

@@ -1,11 +1,13 @@
 """Timing of batched RRT-Connect (vgpu_rrtc.hip: one wave per problem) against a loop of the CPU planner.
 
 P problems from the 16 MotionBenchMaker table_pick problems of tests/golden, each with P / 16 Halton offsets
-(rng_first = 1, 1001, 2001, ...), range 1.0.  Every problem of the fixture has its own scene and a batch call has
-one environment, so the batch is 16 rrtc_batch calls of P / 16 problems each (host arrays in and out, so the copies
-are included); the CPU side is P calls of Robot.rrtc on the CPU rake, on one core and on 16 threads (the calls
-release the GIL).  Prints problems/s of all three, the batch's launches, its iterations and the straggler ratio:
-the largest iteration count of one problem over the mean -- a launch lasts as long as its slowest wave.
+(rng_first = 1, 1001, 2001, ...), range 1.0.  Every problem of the fixture has its own scene, so the batch runs
+in two modes: 16 rrtc_batch calls of P / 16 problems each, one per scene ("batch_*"), and ONE rrtc_batch_scenes
+call of all P problems, each naming its scene ("scenes_*") -- host arrays in and out in both, so the copies are
+included.  The CPU side is P calls of Robot.rrtc on the CPU rake, on one core and on 16 threads (the calls release
+the GIL).  Prints problems/s of all of them, each mode's launches, the iterations and the straggler ratio: the
+largest iteration count of one problem over the mean -- a launch lasts as long as its slowest wave.  Both modes are
+compared with the CPU loop bit for bit ("parity", "scenes_parity").
 Usage: python tools/bench_rrtc_batch.py [n_problems] [reps] [node_cap]
 """
 import json
@@ -62,6 +64,17 @@ def main():
             out += list(zip(got, status, idx))
         return out, launches, iterations, most
 
+    # the same problems in the same order as one multi-scene call
+    envs = [env for env, _, _ in scenes]
+    all_s = np.concatenate([np.tile(s, (per, 1)) for _, s, _ in scenes])
+    all_g = np.concatenate([np.tile(g, (per, 1)) for _, _, g in scenes])
+    all_e = np.repeat(np.arange(n, dtype=np.uint32), per)
+    all_f = np.tile(firsts, n)
+
+    def one_call():
+        got, status, idx = robot.rrtc_batch_scenes(all_s, all_g, envs, all_e, settings, all_f, node_cap, 32, ctx)
+        return list(zip(got, status, idx)), robot.rrtc_stats(ctx)
+
     batch()  # warm-up: uploads the environments, sizes the arena
     times = []
     for _ in range(reps):
@@ -90,6 +103,29 @@ def main():
         times.append(time.perf_counter() - t0)
     call_s = float(np.median(times))
 
+    one_call()  # warm-up: the arena for all P problems, the view table
+    times = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        sgot, sstats = one_call()
+        times.append(time.perf_counter() - t0)
+    scenes_s = float(np.median(times))
+    total = n * per
+    paths = np.zeros((total, 32, 7), np.float32)
+    ln, st = np.zeros(total, np.uint32), np.zeros(total, np.uint8)
+    res = (_lib.VgpuPlanResult * total)()
+    handles = (C.c_void_p * n)(*[env.handle(ctx) for env in envs])
+    times = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        idx = all_f.copy()
+        _lib.check(_lib.load().vgpu_rrtc_batch_scenes_host(
+            ctx.h, C.byref(robot.c_robot), handles, n, all_e.ctypes.data_as(_lib.U32P), all_s.ctypes.data_as(_lib.F32P),
+            all_g.ctypes.data_as(_lib.F32P), 1, total, C.byref(cs), idx.ctypes.data_as(_lib.U64P), node_cap,
+            paths.ctypes.data_as(_lib.F32P), 32, ln.ctypes.data_as(_lib.U32P), res, st.ctypes.data_as(_lib.U8P)), ctx.h)
+        times.append(time.perf_counter() - t0)
+    scenes_call_s = float(np.median(times))
+
     jobs = [(j, k) for j in range(n) for k in range(per)]  # the batch's order
 
     def one(job):
@@ -108,8 +144,13 @@ def main():
         list(pool.map(one, jobs, chunksize=max(len(jobs) // 256, 1)))
         loop16_s = time.perf_counter() - t0
     planner_ns = sum(w.nanoseconds for w, _ in want)  # the searches alone, without the Python call around them
-    parity = all(st != 0 or (a.path.tobytes() == w.path.tobytes() and a.iterations == w.iterations and int(i) == wi)
-                 for (a, st, i), (w, wi) in zip(got, want))
+    def same(results):
+        return len(results) == len(want) and all(
+            st != 0 or (a.path.tobytes() == w.path.tobytes() and a.iterations == w.iterations and int(i) == wi)
+            for (a, st, i), (w, wi) in zip(results, want))
+
+    parity, scenes_parity = same(got), same(sgot)
+    scenes_parity = scenes_parity and [st for _, st, _ in sgot] == [st for _, st, _ in got]
     its = np.array([w.iterations for w, _ in want], np.float64)
     total = len(jobs)
     line = {"workload": "rrtc_batch table_pick", "problems": total, "calls": n, "reps": reps, "node_cap": node_cap,
@@ -119,10 +160,13 @@ def main():
             "batch_c_call_ms": 1e3 * call_s, "batch_c_call_problems_per_s": total / call_s,
             "loop_ms": 1e3 * loop_s, "loop_problems_per_s": total / loop_s, "loop_planner_ms": planner_ns / 1e6,
             "loop16_ms": 1e3 * loop16_s, "loop16_problems_per_s": total / loop16_s,
+            "scenes_parity": bool(scenes_parity), "scenes_ms": 1e3 * scenes_s,
+            "scenes_problems_per_s": total / scenes_s, "scenes_c_call_ms": 1e3 * scenes_call_s,
+            "scenes_c_call_problems_per_s": total / scenes_call_s, "scenes_launches": sstats["launches"],
             "launches": launches, "iterations": iterations, "max_iterations": most,
             "mean_iterations": float(its.mean()), "straggler_ratio": float(its.max() / max(its.mean(), 1e-9))}
     print(json.dumps(line))
-    return 0 if parity else 1
+    return 0 if parity and scenes_parity else 1
 
 
 if __name__ == "__main__":
