@@ -6,7 +6,11 @@ code under test.  Equality is bit for bit: waypoints, length, iterations (and st
 The seeded cage paths are also the batched GPU path's cases (tests/test_gpu_simplify.py imports them); the
 restatement's trace proves that they exercise a shortcut hit short of the last waypoint, a row without any
 valid candidate, accepted and rejected B-spline midpoints, growth beyond twice the input and both outcomes of
-the straight-line test -- otherwise the test fails as "inputs too easy"."""
+the straight-line test -- otherwise the test fails as "inputs too easy".
+
+Section 5 runs the shared case table tests/simplify_cases.py (constructed shortcut rows, long B-spline steps,
+exact result lengths, batches of more than 1024 paths, the Fetch, the UR5 and the Baxter) the same way; the trace's
+CHUNK_EVENTS prove that those cases reach the second 64-lane chunk of each GPU kernel loop."""
 import ctypes as C
 import functools
 
@@ -56,8 +60,27 @@ def path_cost(p):
     return c
 
 
+# what simplify_py counts beyond the original eight keys: the second-chunk branches of the GPU kernels, which
+# work in 64-lane chunks with a carry from one chunk to the next (tests/simplify_cases.py states which case
+# group has to show which of them)
+CHUNK_EVENTS = ("hit_k>=64", "hit_k>=128", "hit_nearest_long", "row_none_over_64", "bs_even_over_64",
+                "bs_cand_slot>=64", "bs_accept_slot>=64", "bs_reject_slot>=64", "bs_gap_before_64")
+
+
 def new_trace():
-    return dict(hit_inner=0, row_none=0, accepted=0, rejected=0, grew=0, straight_ok=0, straight_fail=0, edges=0)
+    """edges: the motions the sequential walk validates; edges_whole: the motions of whole rounds (every
+    candidate of a shortcut row, both edges of every B-spline candidate), what a lockstep batch validates;
+    rounds: straight-line tests + shortcut rows + B-spline steps; cost_segments: len(result) - 1 of every run"""
+    T = dict(hit_inner=0, row_none=0, accepted=0, rejected=0, grew=0, straight_ok=0, straight_fail=0, edges=0,
+             edges_whole=0, rounds=0, cost_segments=set())
+    T.update({k: 0 for k in CHUNK_EVENTS})
+    return T
+
+
+def merge_trace(into, t):
+    for k, v in t.items():
+        into[k] = into[k] | v if isinstance(v, set) else into[k] + v
+    return into
 
 
 def simplify_py(path, validate, trace=None, max_iterations=5, operations=(SHORTCUT, BSPLINE), max_steps=1,
@@ -75,6 +98,7 @@ def simplify_py(path, validate, trace=None, max_iterations=5, operations=(SHORTC
         ok = np.asarray(validate(np.asarray(starts, F), np.asarray(goals, F)), bool)
         hit = np.nonzero(ok)[0]
         T["edges"] += int(hit[0]) + 1 if len(hit) else len(ok)
+        T["edges_whole"] += len(ok)
         return int(hit[0]) if len(hit) else None
 
     def shortcut():
@@ -86,10 +110,17 @@ def simplify_py(path, validate, trace=None, max_iterations=5, operations=(SHORTC
         while i < len(p) - 2:
             js = list(range(len(p) - 1, i + 1, -1))
             k = first_valid([p[i]] * len(js), [p[j] for j in js])
+            T["rounds"] += 1
             if k is None:
                 T["row_none"] += 1
+                T["row_none_over_64"] += len(js) > 64
             else:
                 T["hit_inner"] += js[k] != len(p) - 1
+                T["hit_k>=64"] += k >= 64
+                T["hit_k>=128"] += k >= 128
+                # the erase moves the (len - j) waypoints from j on down by j - i - 1 waypoints: by one, and more
+                # than a chunk of floats, source and destination overlap inside every chunk
+                T["hit_nearest_long"] += js[k] == i + 2 and (len(p) - js[k]) * p.shape[1] > 64
                 p = np.concatenate([p[:i + 1], p[js[k]:]])
                 result = True
             i += 1
@@ -110,20 +141,32 @@ def simplify_py(path, validate, trace=None, max_iterations=5, operations=(SHORTC
                 q[2 * i + 1] = interpolate(p[i], p[i + 1], 0.5)
             p = q
             updated = False
-            for index in range(2, len(p) - 1, 2):
+            T["rounds"] += 1
+            evens = range(2, len(p) - 1, 2)
+            T["bs_even_over_64"] += len(evens) > 64
+            slot, gap_before_64, cand_past_64 = 0, False, False  # slot: the candidate's place in the compact list
+            for t, index in enumerate(evens):
                 t1 = interpolate(p[index], p[index - 1], midpoint)
                 t2 = interpolate(p[index], p[index + 1], midpoint)
                 mid = interpolate(t1, t2, 0.5)
                 if not l2((mid - p[index]).astype(F)) > F(min_change):
+                    gap_before_64 |= t < 64
                     continue
+                cand_past_64 |= t >= 64
                 ok = np.asarray(validate(np.stack([p[index - 1], mid]), np.stack([mid, p[index + 1]])), bool)
                 T["edges"] += 2 if ok[0] else 1
+                T["edges_whole"] += 2
+                T["bs_cand_slot>=64"] += slot >= 64
                 if ok[0] and ok[1]:
                     p[index] = mid
                     changed = updated = True
                     T["accepted"] += 1
+                    T["bs_accept_slot>=64"] += slot >= 64
                 else:
                     T["rejected"] += 1
+                    T["bs_reject_slot>=64"] += slot >= 64
+                slot += 1
+            T["bs_gap_before_64"] += gap_before_64 and cand_past_64
             if not updated:
                 break
         return changed
@@ -133,6 +176,8 @@ def simplify_py(path, validate, trace=None, max_iterations=5, operations=(SHORTC
     if len(p) > 2:
         straight = bool(np.asarray(validate(p[:1], p[-1:]), bool)[0])
         T["edges"] += 1
+        T["edges_whole"] += 1
+        T["rounds"] += 1
         T["straight_ok" if straight else "straight_fail"] += 1
     if straight:
         p = np.stack([p[0], p[-1]])
@@ -148,6 +193,7 @@ def simplify_py(path, validate, trace=None, max_iterations=5, operations=(SHORTC
             if not any_ or status:
                 break
     T["grew"] += len(p) > 2 * n_in
+    T["cost_segments"].add(len(p) - 1)
     return p, iterations, status
 
 
@@ -216,7 +262,7 @@ def test_cage_paths_match_restatement(vamp, oracle, base):
     print("trace", base, T)
     # at base (200, 200, 0) the arm stands clear of the cage (every straight line is valid): the conditions are
     # asserted over the whole case set, both bases together
-    seen = {k: sum(cage_expected(b)[1][k] for b in BASES) for k in T}
+    seen = {k: sum(cage_expected(b)[1][k] for b in BASES) for k in T if k != "cost_segments"}
     easy = [k for k in ("hit_inner", "row_none", "accepted", "rejected", "grew", "straight_ok", "straight_fail")
             if not seen[k]]
     assert not easy, f"inputs too easy: never seen {easy} ({seen})"
@@ -392,3 +438,31 @@ def test_unsupported_and_defaults(vamp, oracle):
                                len(long), C.byref(cs), np.empty((4, 7), F).ctypes.data_as(_lib.F32P), 4, C.byref(res),
                                None)
     assert rc == -1 and res.path_len == len(exp[name][0])
+
+
+# ---- 5. the shared case table (tests/simplify_cases.py): the settings, robots and chunk-boundary paths at which
+# tests/test_gpu_simplify.py compares the batch with this function --------------------------------------------------
+import simplify_cases as sc  # noqa: E402  (it imports the restatement above)
+
+
+@pytest.mark.parametrize("group", sc.GROUPS)
+def test_case_group_shows_its_events(oracle, group):
+    assert {c.group for c in sc.cases().values()} == set(sc.GROUPS)
+    print("seen", group, sc.check_group(group))
+
+
+@pytest.mark.parametrize("name", sc.CASE_NAMES)
+def test_case_table_matches_restatement(vamp, oracle, name):
+    case = sc.cases()[name]
+    runs, T = sc.restated(name)
+    robot, env = sc.product(vamp, case)
+    settings = make_settings(vamp, case.cpu_keywords())
+    edges = 0
+    for (pname, p), (want, it, st, _) in zip(case.paths, runs):
+        res = robot.simplify(p, env, settings)
+        assert (len(res.path), res.iterations, res.status) == (len(want), it, st), \
+            (pname, len(res.path), len(want), res.iterations, it, res.status, st)
+        assert same_path(res.path, want), pname
+        assert np.float32(res.cost).view(np.uint32) == path_cost(want).view(np.uint32), pname
+        edges += res.validated_edges
+    assert edges == T["edges"]
